@@ -1,8 +1,13 @@
 """bench.py — spaced-k-mer sketch + ANI engine on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up config 3, warms up, times the K headline steps and prints
+the result line.  --dump-outputs DIR also writes the sketch set the last timed
+step returned (rank 0's) as DIR/*.npy.  --full adds every other figure
+described below to the same line.
 
 Headline (`value`): k-mers hashed/s, whole job, on config 3 of BASELINE.json
 (one 3 Gb human-scale synthetic genome per GPU: 24 contigs x 125 Mb, four 10 kb
@@ -10,12 +15,12 @@ N-runs per contig, spaced seed w=31/k=21 mask seed 0, FracMinHash 1/1000).
 A step = one complete sketch build of that genome (fused scan kernel + sort +
 unique, host syncs included) with the bytes already resident in HBM. The timed
 steps run with --inflight (default 3) builds in flight, one context and HIP
-stream each, so one build's post-processing overlaps the next build's scan; a
-serial pass (`ms_per_step_serial`) and the scan kernel's own time are reported
-beside it.
+stream each, so one build's post-processing overlaps the next build's scan;
+with --full a serial pass (`ms_per_step_serial`) and the scan kernel's own time
+are reported beside it.
 Genomes are independent, so ranks shard them with no collective: weak scaling.
 
-Secondary (`pairs`): genome-pairs ANI/s on config 4 (1000 x 5 Mb genomes =
+Secondary (--full, `pairs`): genome-pairs ANI/s on config 4 (1000 x 5 Mb genomes =
 10 ancestors x 100 mutated descendants, w=31/k=21, bottom-s s=10000), strong
 scaling.  A pair step is what the reference's "Time taken for comparison"
 covers (kmer-sketching.cpp:185-203): every ordered pair's intersection count,
@@ -31,7 +36,7 @@ the same leg at w = 45 / k = 30 (128-bit k-mers).
 
 `cpu_baseline`: the reference-faithful CPU port (oracle/ref_port.cpp, see
 BASELINE.md) timed on this box's host cores on a bounded sample of the same
-workload (rank 0, N=1 only).
+workload (--full, rank 0, N=1 only).
 """
 import argparse
 import json
@@ -173,9 +178,12 @@ def make_c3(ctx, seed_base):
     return buf, n_bytes
 
 
-def run_c3_inflight(device, buf, n_bytes, mask, steps, inflight, world):
+def run_c3_inflight(device, buf, n_bytes, mask, steps, inflight, world, keep_last=False):
     """K config-3 builds with `inflight` of them in flight; returns (whole-job
-    k-mers/s, max-over-ranks seconds, set of sketch sizes)."""
+    k-mers/s, max-over-ranks seconds, set of sketch sizes, last set).  With
+    `keep_last` the set of the last step (index K - 1) is handed back to the
+    caller instead of being freed in stream order; otherwise the last set is
+    None."""
     import threading
     inflight = max(1, inflight)
     streams = [torch.cuda.Stream() for _ in range(inflight)]
@@ -190,12 +198,16 @@ def run_c3_inflight(device, buf, n_bytes, mask, steps, inflight, world):
         del del_
     kept = [[] for _ in ctxs]
     errors = []
+    last = []
 
     def worker(i):
         try:
-            for _ in range(i, steps, inflight):
+            for s in range(i, steps, inflight):
                 ss = build(ctxs[i])
                 kept[i].append((int(ss.windows()[0]), int(ss.sizes()[0])))
+                if keep_last and s == steps - 1:
+                    last.append(ss)
+                    continue
                 # stream-ordered free: the arrays return to the block cache
                 # without waiting for the other build in flight
                 ss.free(stream=streams[i].cuda_stream)
@@ -220,7 +232,20 @@ def run_c3_inflight(device, buf, n_bytes, mask, steps, inflight, world):
     assert windows == steps * c3_windows(), (windows, steps * c3_windows())
     del kept
     total = sum_over_ranks(windows, world)
-    return total / elapsed, elapsed, sizes
+    return total / elapsed, elapsed, sizes, (last[0] if last else None)
+
+
+def dump_c3_outputs(d, ss):
+    """--dump-outputs: what the caller of the last timed config-3 build
+    received, as float64 .npy files in `d` (48 MB in all).  The sketch is the
+    sorted u64 hash set; a float64 holds 53 bits, so each value is written as
+    its high and low 32-bit halves (value = hi * 2**32 + lo), both exact."""
+    os.makedirs(d, exist_ok=True)
+    sk = ss.sketch(0)[:, 0]
+    np.save(os.path.join(d, "sketch_hi32.npy"), (sk >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(d, "sketch_lo32.npy"), (sk & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(d, "sizes.npy"), ss.sizes().astype(np.float64))
+    np.save(os.path.join(d, "windows.npy"), ss.windows().astype(np.float64))
 
 
 def run_end_to_end(ctx, mask, buf, steps):
@@ -1349,6 +1374,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the serial pass and rooflines, configs 2, 4 and 5, the "
+                         "end-to-end and sharded legs, the reference sweep and the CPU baselines "
+                         "(the --no-* options below choose among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's sketch set to DIR/*.npy (float64)")
     ap.add_argument("--cpu-sample-mb", type=int, default=125)  # ~10 s of 1-core work
     ap.add_argument("--cpu-crosscheck-mb", type=int, default=400)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1396,13 +1427,54 @@ def main():
     for _ in range(args.warmup):
         ss = step()
         del ss
-    # serial pass: one build at a time on the null stream; gives the scan
+    # --full, serial pass: one build at a time on the null stream; gives the scan
     # kernel's own duration for the roofline and the unpipelined step time
+    serial = run_c3_serial(ctx, step, args.steps, world) if args.full else None
+
+    # headline pass: `inflight` builds at once (host threads, one context per
+    # HIP stream), so one build's sort / unique / host syncs run under the next
+    # build's scan. Each build is complete when sks_sketch_build returns; its
+    # set is then freed in stream order (sks_sketch_set_free_on_stream).
+    dump = args.dump_outputs is not None and rank == 0
+    value, elapsed, inflight_sizes, last = run_c3_inflight(local, buf, n_bytes, mask, args.steps,
+                                                           args.inflight, world, keep_last=dump)
+    assert len(inflight_sizes) == 1, inflight_sizes
+    sketch_size = next(iter(inflight_sizes))
+    if serial is not None:
+        assert inflight_sizes == {serial["sizes"][0]}, (inflight_sizes, serial["sizes"][0])
+    if dump:
+        dump_c3_outputs(args.dump_outputs, last)
+        last.free()
+    del last
+
+    line = {
+        "metric": METRIC, "value": value, "unit": "k-mers/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "u64", "full": args.full,
+        "data": "synthetic (device splitmix64 generator, resident in HBM)",
+        "config": {"workload": "config3: 1x3 Gb multi-contig genome per GPU, spaced seed "
+                               "w=31/k=21 (mask seed 0), FracMinHash 1/1000",
+                   "builds_in_flight": args.inflight,
+                   "genome_bytes": n_bytes, "windows_per_genome": c3_windows(),
+                   "sketch_size": sketch_size, "parallelism": f"genome-sharded x{world}"},
+    }
+    if args.full:
+        line.update(run_full(args, ctx, world, rank, mask, buf, n_bytes, serial))
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if collective():
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def run_c3_serial(ctx, step, steps, world):
+    """The --full serial pass over config 3: `steps` builds one after another."""
     barrier(world)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     scan_ms, survivors, windows, sizes = [], [], 0, []
-    for _ in range(args.steps):
+    for _ in range(steps):
         ss = step()
         t = ctx.timings()
         scan_ms.append(t["scan_ms"])
@@ -1412,17 +1484,18 @@ def main():
         del ss
     torch.cuda.synchronize()
     barrier(world)
-    elapsed_serial = max_over_ranks(time.perf_counter() - t0, world)
-    sum_windows_serial = sum_over_ranks(windows, world)
-    assert windows == args.steps * c3_windows(), (windows, c3_windows())
+    elapsed = max_over_ranks(time.perf_counter() - t0, world)
+    sum_windows = sum_over_ranks(windows, world)
+    assert windows == steps * c3_windows(), (windows, c3_windows())
+    return {"scan_ms": scan_ms, "survivors": survivors, "sizes": sizes, "elapsed": elapsed,
+            "sum_windows": sum_windows}
 
-    # headline pass: `inflight` builds at once (host threads, one context per
-    # HIP stream), so one build's sort / unique / host syncs run under the next
-    # build's scan. Each build is complete when sks_sketch_build returns; its
-    # set is then freed in stream order (sks_sketch_set_free_on_stream).
-    value, elapsed, inflight_sizes = run_c3_inflight(local, buf, n_bytes, mask, args.steps,
-                                                     args.inflight, world)
-    assert inflight_sizes == {sizes[0]}, (inflight_sizes, sizes[0])
+
+def run_full(args, ctx, world, rank, mask, buf, n_bytes, serial):
+    """Everything --full adds to the result line: the serial pass's figures and
+    the scan's rooflines, then the other workloads and the CPU baselines."""
+    scan_ms, survivors = serial["scan_ms"], serial["survivors"]
+    elapsed_serial, sum_windows_serial = serial["elapsed"], serial["sum_windows"]
 
     # roofline of the dominant kernel (fused scan): algorithmic bytes per launch
     # = input bytes read (1 B per sequence byte incl. separators) + 8 B per record written
@@ -1470,43 +1543,28 @@ def main():
         cpu = cpu_baseline_c3(mask, args.cpu_sample_mb * 1_000_000)
         cpu_x = cpu_crosscheck_c3(ctx, buf, mask, args.cpu_crosscheck_mb * 1_000_000)
 
-    if rank == 0:
-        line = {
-            "metric": METRIC, "value": value, "unit": "k-mers/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "ms_per_step_serial": elapsed_serial / args.steps * 1e3,
-            "value_serial": sum_windows_serial / elapsed_serial,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u64",
-            "data": "synthetic (device splitmix64 generator, resident in HBM)",
-            "config": {"workload": "config3: 1x3 Gb multi-contig genome per GPU, spaced seed "
-                                   "w=31/k=21 (mask seed 0), FracMinHash 1/1000",
-                       "builds_in_flight": args.inflight,
-                       "genome_bytes": n_bytes, "windows_per_genome": c3_windows(),
-                       "sketch_size": sizes[0], "parallelism": f"genome-sharded x{world}"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": "scan_kernel<frac, boost-mix, pre-filter>", "kernel_ms": scan_avg_ms,
-                         "kernel_ms_median": float(np.median(scan_ms)),
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         "traffic_source": traffic_src, "traffic_note": traffic_note,
-                         "valu": scan_valu_roofline(scan_avg_ms),
-                         "timing": "hipEvents around each scan launch of the serial pass "
-                                   "(the --steps builds after --warmup)"},
-            "cpu_baseline": cpu,
-            "cpu_crosscheck": cpu_x,
-            "config2": c2,
-            "pairs": pairs,
-            "pairs_wide": pairs_wide,
-            "seed_sweep": sweep,
-            "reference_sweep": ref_sweep,
-            "end_to_end": e2e,
-            "c3_one_genome_sharded": c3s,
-        }
-        print(json.dumps(line), flush=True)
-    if collective():
-        import torch.distributed as dist
-        dist.destroy_process_group()
+    return {
+        "ms_per_step_serial": elapsed_serial / args.steps * 1e3,
+        "value_serial": sum_windows_serial / elapsed_serial,
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                     "kernel": "scan_kernel<frac, boost-mix, pre-filter>", "kernel_ms": scan_avg_ms,
+                     "kernel_ms_median": float(np.median(scan_ms)),
+                     "algorithmic_bytes_per_launch": alg_bytes,
+                     "traffic_source": traffic_src, "traffic_note": traffic_note,
+                     "valu": scan_valu_roofline(scan_avg_ms),
+                     "timing": "hipEvents around each scan launch of the serial pass "
+                               "(the --steps builds after --warmup)"},
+        "cpu_baseline": cpu,
+        "cpu_crosscheck": cpu_x,
+        "config2": c2,
+        "pairs": pairs,
+        "pairs_wide": pairs_wide,
+        "seed_sweep": sweep,
+        "reference_sweep": ref_sweep,
+        "end_to_end": e2e,
+        "c3_one_genome_sharded": c3s,
+    }
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@
 # alternating, two passes; prints value / ms_per_step / scan kernel mean
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
-C3="--no-pairs --no-sweep --no-e2e --no-c3-sharded --no-c2 --no-cpu-baseline --steps 20 --warmup 2"
+C3="--full --no-pairs --no-sweep --no-e2e --no-c3-sharded --no-c2 --no-cpu-baseline --steps 20 --warmup 2"
 for pass in 1 2; do
   for mode in static dyn; do
     if [ $mode = static ]; then export SKS_SCAN_STATIC=1; else unset SKS_SCAN_STATIC; fi

@@ -34,7 +34,7 @@ check)
   tail -1 $O/tests.log
   $T 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
   tail -2 $O/smoke.log
-  $T 900 python3 bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  $T 900 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   tail -c 600 $O/bench.json ;;
 tests)
   O=$R/gpurun_out/${1:-tests}; shift; mkdir -p $O; cd $R
@@ -43,7 +43,7 @@ tests)
   tail -3 $O/tests.log ;;
 bench)
   O=$R/gpurun_out/${1:-bench}; shift; mkdir -p $O; cd $R
-  $T 900 python3 bench.py "$@" > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  $T 900 python3 bench.py --full "$@" > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   tail -c 1500 $O/bench.json ;;
 profile)
   cd $R && $T 1100 bash tools/profile_round.sh "$1" ;;
@@ -67,7 +67,7 @@ ab)
   done ;;
 rehearse)
   O=$R/gpurun_out/${1:-reh}; mkdir -p $O; cd $R
-  NB="--no-sweep --no-e2e --no-cpu-baseline --no-c2 --steps 3 --warmup 1"
+  NB="--full --no-sweep --no-e2e --no-cpu-baseline --no-c2 --steps 3 --warmup 1"
   $T 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
     --master-port 29517 bench.py --dist-rehearsal $NB > $O/bench_1rank_rccl.json 2> $O/bench_1rank_rccl.err \
     || { tail -20 $O/bench_1rank_rccl.err; exit 1; }

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round profile (GPU box, repo root):  bash tools/profile_round.sh r02
-# 1. kernel trace + stats of the DEFAULT bench command (bench.py --steps 20
-#    --warmup 2, what the driver runs); the scan launches bench.py times are the
+# 1. kernel trace + stats of the whole bench command (bench.py --full --steps 20
+#    --warmup 2); the scan launches bench.py times are the
 #    serial pass, dispatches [warmup, warmup + steps) of the config-3 scan kernel.
 # 2. PMC passes over the same command limited to its config-3 part (identical
 #    scan dispatch sequence): FETCH_SIZE and WRITE_SIZE in separate passes
@@ -17,7 +17,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/round_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="$R/bench.py --steps $STEPS --warmup $WARMUP"
+ARGS="$R/bench.py --full --steps $STEPS --warmup $WARMUP"
 C3="--no-pairs --no-sweep --no-e2e --no-c3-sharded --no-c2 --no-cpu-baseline"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 $ARGS > $OUT/bench_traced.json 2> $OUT/trace.log
 echo "trace done"
