@@ -18,8 +18,12 @@
 // range of 4096-window tiles.  A tile's bytes arrive with 16-B coalesced
 // loads (prefetched one tile ahead into registers), are packed once into
 // 2-bit words in LDS (a big-endian stream for F, a complemented little-endian
-// stream for R, a 1-bit invalid map), and every lane then owns 16 consecutive
-// window starts, extracting F and R with funnel shifts (v_alignbit_b32).
+// stream for R, a 1-bit invalid map).  The narrow kernel's lane (g, r) — r the
+// low 4 bits of the thread index, g the rest — then owns the 16 window starts
+// 16 (16 g + m) + r, m = 0..15: 16 bases apart, so consecutive windows of a
+// lane share a 32-bit word of F and of R and each window costs one new funnel
+// shift (v_alignbit_b32) per strand, by a per-lane constant amount.  (The wide
+// kernel's lanes own 16 consecutive starts.)
 // Survivors (~1/c of windows) go to an LDS queue flushed with one global
 // atomic per flush, so the global counters see a few thousand atomics per
 // launch instead of one per survivor.
@@ -126,9 +130,9 @@ __device__ __forceinline__ uint32_t funnel(uint32_t hi, uint32_t lo, uint32_t s)
 // without overlapping), and validity of all 4 bytes is one v_sad_u8 against
 // the expected lower-case letters.  Only a 16-base word holding a non-ACGT
 // byte pays for the exact per-byte invalid bits (encode4).
-// ALIGNED: the tile's bytes start on a dword boundary (sb == 0, wave-uniform;
-// a genome starting at a 4-byte multiple, e.g. config 3), so the dwords are
-// used as they are and the four alignbits go.
+// ALIGNED: x[0..3] are the word's dwords as they are (the pack from the
+// prefetch registers of a tile that starts on a 16-byte boundary, e.g. config
+// 3), so the four alignbits go.
 template <bool ALIGNED>
 __device__ __forceinline__ void pack16(const uint32_t (&x)[5], uint32_t sb, uint32_t& le,
                                        uint32_t& inv) {
@@ -266,14 +270,24 @@ __device__ __forceinline__ bool keep_fmh(const ScanParams& p, uint64_t f, uint64
 
 constexpr int kBeOff = 2;  // s_be[kBeOff + i] = word i; two zero words in front
 
-#ifndef SKS_SCAN_MIN_WAVES
-#define SKS_SCAN_MIN_WAVES 1
+// Waves per SIMD the compiler must leave room for (its register budget is
+// 512 / waves): 7 for the pre-filter kernel (what its ~100 SGPRs allow, and
+// what the runtime's occupancy query answers), 4 for list mode with its large
+// queue, 5 for the rest.  Without it the compiler spends registers on hoisted
+// addresses and a whole wave per SIMD goes.
+template <int MODE, int PRE>
+constexpr int min_waves() {
+#ifdef SKS_SCAN_MIN_WAVES
+  return SKS_SCAN_MIN_WAVES;
+#else
+  return PRE ? 7 : MODE == kModeList ? 4 : 5;
 #endif
+}
 
 constexpr uint32_t kCandCap = 128;  // pre-filter candidates per wave (< 64 + 64)
 
 template <int MODE, int FLAVOUR, int PRE = 0>
-__global__ __launch_bounds__(kBlock, SKS_SCAN_MIN_WAVES) void scan_kernel(ScanParams p) {
+__global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(ScanParams p) {
   __shared__ uint32_t s_raw[kLoadVecs * 4];
   __shared__ uint32_t s_be[kWords + 2 + kBeOff];
   __shared__ uint32_t s_lc[kWords + 2];
@@ -313,11 +327,25 @@ __global__ __launch_bounds__(kBlock, SKS_SCAN_MIN_WAVES) void scan_kernel(ScanPa
   // base b - (32 - w): its low 2w bits are F, the bits above are older bases
   // that the mask (bits < 2w) removes, so no per-window shift is needed.
   const uint32_t dshift = 2 * (32 - w);          // 0..62 bits
-  const bool dword = dshift >= 32;
-  const uint32_t dbits = dshift & 31;
   const uint64_t wmask_bits = (w >= 64) ? ~0ull : ((1ull << w) - 1);
-  const uint64_t region_bits = (kWPT - 1 + w >= 64) ? ~0ull : ((1ull << (kWPT - 1 + w)) - 1);
   if (tid < kBeOff) s_be[tid] = 0;
+  // Lane (grp, r) owns the window starts 16 (16 grp + m) + r, m = 0..15: word
+  // wbase + m of the tile, base r of it.  With P(m) the 32 BE bits from bit
+  // 2r - dshift of word wbase + m and Q(m) the 32 LC bits from bit 2r of it,
+  //   F(m) = P(m) : P(m + 1)      R(m) = Q(m + 1) : Q(m)
+  // so a window adds one word and one funnel shift per strand to its
+  // predecessor's.  2r - dshift + 64 = 32 qf + st with st in [1, 32]: P(m) starts
+  // st bits into word wbase + m - 2 + qf, i.e. it is that word and the next
+  // shifted right by 32 - st in [0, 31] (st = 32 is the next word itself, which
+  // a shift of 0 gives; the kBeOff zero words cover wbase + m - 2 + qf < 0).
+  const uint32_t r = tid & 15;
+  const uint32_t wbase = (uint32_t)(tid >> 4) * kWPT;
+  const uint32_t of = 2 * r + 64 - dshift;  // 2..94
+  const uint32_t qf = (of - 1) >> 5;        // 0..2
+  const uint32_t sF = 32 * qf + 32 - of;    // 0..31
+  const uint32_t sR = 2 * r;
+  const uint32_t* const fb = s_be + (kBeOff - 2) + wbase + qf;  // fb[m], fb[m + 1] -> P(m)
+  const uint32_t* const rb = s_lc + wbase;                      // rb[m], rb[m + 1] -> Q(m)
 
   // segment cursors (wave-uniform) for the current tile and the prefetch
   uint32_t seg_lo = 0, seg_hi = p.n_seg;
@@ -354,34 +382,52 @@ __global__ __launch_bounds__(kBlock, SKS_SCAN_MIN_WAVES) void scan_kernel(ScanPa
       if (last_of_chunk) s_next = grab;
     }
 
-    // 1) raw bytes -> LDS
-    reinterpret_cast<uint4*>(s_raw)[tid] = v0;
-    if (tid < kLoadVecs - kBlock) reinterpret_cast<uint4*>(s_raw)[kBlock + tid] = v1;
-    __syncthreads();
-    // the next tile: the chunk's next, else the next chunk's first (read here,
-    // after the barrier; s_next is rewritten only at the next chunk's last tile)
-    const uint64_t next_tile = !last_of_chunk ? tile + 1 : dyn ? (uint64_t)s_next : p.n_tiles;
-
-    // 2) pack: word i covers bases [16 i, 16 i + 16) of the tile
-    {
+    // 1) + 2) pack: word i covers bases [16 i, 16 i + 16) of the tile
+    auto store_word = [&](int i, uint32_t le, uint32_t inv) {
+      s_be[kBeOff + i] = rev_pairs(le);
+      s_lc[i] = ~le;
+      s_inv[i] = inv;
+    };
+    if (shift == 0) {
+      // the tile starts on a 16-byte boundary (wave-uniform; every tile of a
+      // genome that does, e.g. config 3): lane tid's prefetched vector is word
+      // tid and lanes 0..3 hold the halo words, so they are packed from the
+      // registers without the trip through s_raw and its barrier
+      uint32_t le, inv;
+      const uint32_t x0[5] = {v0.x, v0.y, v0.z, v0.w, 0u};
+      pack16<true>(x0, 0, le, inv);
+      store_word(tid, le, inv);
+      if (tid < kHaloWords) {
+        const uint32_t x1[5] = {v1.x, v1.y, v1.z, v1.w, 0u};
+        pack16<true>(x1, 0, le, inv);
+        store_word(kBlock + tid, le, inv);
+      }
+    } else {
+      reinterpret_cast<uint4*>(s_raw)[tid] = v0;
+      if (tid < kLoadVecs - kBlock) reinterpret_cast<uint4*>(s_raw)[kBlock + tid] = v1;
+      __syncthreads();
       const uint32_t sb = (shift & 3) * 8;  // wave-uniform
-      auto pack_words = [&](auto aligned) {
-        for (int i = tid; i < kWords; i += kBlock) {
-          const uint32_t wi = (16 * i + shift) >> 2;  // dword offset in s_raw
-          uint32_t x[5];
+      for (int i = tid; i < kWords; i += kBlock) {
+        const uint32_t wi = (16 * i + shift) >> 2;  // dword offset in s_raw
+        uint32_t x[5];
 #pragma unroll
-          for (int k = 0; k < 5; ++k) x[k] = (decltype(aligned)::value && k == 4) ? 0u : s_raw[wi + k];
-          uint32_t le, inv;
-          pack16<decltype(aligned)::value>(x, sb, le, inv);
-          s_be[kBeOff + i] = rev_pairs(le);
-          s_lc[i] = ~le;
-          s_inv[i] = inv;
-        }
-      };
-      if (sb == 0) pack_words(std::true_type{});
-      else pack_words(std::false_type{});
+        for (int k = 0; k < 5; ++k) x[k] = s_raw[wi + k];
+        uint32_t le, inv;
+        pack16<false>(x, sb, le, inv);
+        store_word(i, le, inv);
+      }
     }
     __syncthreads();
+    // the next tile: the chunk's next, else the next chunk's first (read here,
+    // after the barrier; s_next is rewritten only at the next chunk's last
+    // tile).  Every lane reads the same value: readfirstlane keeps the tile
+    // counters and their 64-bit compares on the scalar unit.
+    uint64_t next_tile = !last_of_chunk ? tile + 1 : p.n_tiles;
+    if (last_of_chunk && dyn) {
+      const unsigned long long sn = s_next;
+      next_tile = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(sn >> 32)) << 32) |
+                  __builtin_amdgcn_readfirstlane((uint32_t)sn);
+    }
 
     // 3) prefetch the next tile while this one is hashed
     if (next_tile < (dyn ? p.n_tiles : t_end)) {
@@ -391,31 +437,85 @@ __global__ __launch_bounds__(kBlock, SKS_SCAN_MIN_WAVES) void scan_kernel(ScanPa
       if (tid < kLoadVecs - kBlock) v1 = load_vec(p.seq, pf_base, kBlock + tid, (int64_t)ng.seg_end);
     }
 
-    // 4) 16 windows per lane: starts 16*tid + j
-    uint32_t be[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) be[k] = s_be[kBeOff + tid - 2 + k];  // words tid-2 .. tid+2
-    uint32_t bs[3];  // BE words shifted back by (32 - w) bases
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const uint32_t hi = dword ? be[k] : be[k + 1];
-      const uint32_t lo = dword ? be[k + 1] : be[k + 2];
-      bs[k] = funnel(hi, lo, dbits);
-    }
-    const uint32_t lc0 = s_lc[tid], lc1 = s_lc[tid + 1], lc2 = s_lc[tid + 2];
-    const uint64_t inv64 = (uint64_t)s_inv[tid] | ((uint64_t)s_inv[tid + 1] << 16) |
-                           ((uint64_t)s_inv[tid + 2] << 32) | ((uint64_t)s_inv[tid + 3] << 48);
-    const bool lane_clean = (inv64 & region_bits) == 0;
-    // canonical masked k-mer of window j (runtime j allowed)
-    auto canon = [&](uint32_t j) -> uint64_t {
-      const uint32_t fh = j ? funnel(bs[0], bs[1], 32 - 2 * j) : bs[0];
-      const uint32_t fl = j ? funnel(bs[1], bs[2], 32 - 2 * j) : bs[1];
+    // 4) 16 windows per lane: starts 16 (wbase + m) + r
+    // A wave's windows read the invalid map of its 64 words and of the 2 after
+    // them (bases up to 15 + 31 past its last word's first).
+    const int lane = tid & 63;
+    bool dirty = s_inv[tid] != 0;
+    if (lane < 2) dirty = dirty || s_inv[(tid | 63) + 1 + lane] != 0;
+    const bool wave_clean = !__any(dirty);
+    auto canon_of = [&](uint32_t fh, uint32_t fl, uint32_t rh, uint32_t rl) -> uint64_t {
       const uint64_t F = (((uint64_t)fh) << 32) | fl;
-      const uint32_t rl = j ? funnel(lc1, lc0, 2 * j) : lc0;
-      const uint32_t rh = j ? funnel(lc2, lc1, 2 * j) : lc1;
       const uint64_t R = (((uint64_t)rh) << 32) | rl;
       const uint64_t fm = F & p.mask_lo, rm = R & p.mask_lo;
       return fm < rm ? fm : rm;
+    };
+    // canonical masked k-mer of window m, re-read from LDS (run-time m: the
+    // survivors of the keep-mask loop)
+    auto canon_at = [&](uint32_t m) -> uint64_t {
+      const uint32_t f0 = fb[m], f1 = fb[m + 1], f2 = fb[m + 2];
+      const uint32_t r0 = rb[m], r1 = rb[m + 1], r2 = rb[m + 2];
+      return canon_of(funnel(f0, f1, sF), funnel(f1, f2, sF), funnel(r2, r1, sR), funnel(r1, r0, sR));
+    };
+    // The walk of a wave that holds an invalid base (rare; a loop, to keep it out
+    // of the unrolled code): body(m, c, valid).  Same carried words as the clean
+    // walk, plus the invalid map: window m is valid iff bits [r, r + w) of the
+    // map from word wbase + m are 0 (r + w <= 47: three 16-bit words).  Words up
+    // to wbase + 18 are read (the last unused): all inside the packed tile.
+    auto for_windows_checked = [&](auto body) {
+      const uint32_t* const ib = s_inv + wbase;
+      uint32_t fw = fb[1], rw = rb[1];
+      uint32_t fp = funnel(fb[0], fw, sF), rp = funnel(rw, rb[0], sR);
+      uint32_t i0 = ib[0], i1 = ib[1];
+      // the reads run one window ahead where registers allow (not in the
+      // pre-filter kernel, which sits at its occupancy's register limit)
+      uint32_t fnext = 0, rnext = 0, inext = 0;
+      if constexpr (!PRE) {
+        fnext = fb[2];
+        rnext = rb[2];
+        inext = ib[2];
+      }
+#pragma unroll 1
+      for (int m = 0; m < kWPT; ++m) {
+        uint32_t fw2, rw2, i2;
+        if constexpr (PRE) {
+          fw2 = fb[m + 2];
+          rw2 = rb[m + 2];
+          i2 = ib[m + 2];
+        } else {
+          fw2 = fnext;
+          rw2 = rnext;
+          i2 = inext;
+          fnext = fb[m + 3];
+          rnext = rb[m + 3];
+          inext = ib[m + 3];
+        }
+        const uint32_t fn = funnel(fw, fw2, sF), rn = funnel(rw2, rw, sR);
+        const uint64_t iv = (uint64_t)i0 | ((uint64_t)i1 << 16) | ((uint64_t)i2 << 32);
+        body(m, canon_of(fp, fn, rn, rp), ((iv >> r) & wmask_bits) == 0);
+        fw = fw2; rw = rw2; fp = fn; rp = rn; i0 = i1; i1 = i2;
+      }
+    };
+    // The clean wave's unrolled walk over its 16 windows: body(m, c) gets the
+    // canonical k-mer; each step reads one new word per strand, one window
+    // ahead of its use.  The compiler barrier keeps the reads there: hoisted to
+    // the top, the 36 words would cost the registers that set the occupancy.
+    auto for_windows = [&](auto body) {
+      uint32_t fw = fb[1], rw = rb[1];
+      uint32_t fp = funnel(fb[0], fw, sF), rp = funnel(rw, rb[0], sR);
+      uint32_t fnext = fb[2], rnext = rb[2];
+#pragma unroll
+      for (int m = 0; m < kWPT; ++m) {
+        const uint32_t fw2 = fnext, rw2 = rnext;
+        if (m + 1 < kWPT) {
+          fnext = fb[m + 3];
+          rnext = rb[m + 3];
+        }
+        asm volatile("" ::: "memory");
+        const uint32_t fn = funnel(fw, fw2, sF), rn = funnel(rw2, rw, sR);
+        body(m, canon_of(fp, fn, rn, rp));
+        fw = fw2; rw = rw2; fp = fn; rp = rn;
+      }
     };
     // Hot loop: no branches — one keep bit per window, so the compiler can
     // interleave the 16 independent hash chains.  Survivors (~1/c) are
@@ -425,7 +525,6 @@ __global__ __launch_bounds__(kBlock, SKS_SCAN_MIN_WAVES) void scan_kernel(ScanPa
       // min(s, 4) bits of its fmh are zero, and those follow from the low 32
       // bits of the last multiply. Windows passing that test (1/8 for c = 1000)
       // are queued per wave in LDS and finished 64 at a time, all lanes busy.
-      const int lane = tid & 63;
       // the wave's candidate buffer, wave-uniform: readfirstlane keeps it in an
       // SGPR so a candidate's LDS address is one v_lshl_add_u32 of its rank
       ulonglong2* cb = s_cand + __builtin_amdgcn_readfirstlane(tid >> 6) * kCandCap;
@@ -449,16 +548,10 @@ __global__ __launch_bounds__(kBlock, SKS_SCAN_MIN_WAVES) void scan_kernel(ScanPa
         }
         __builtin_amdgcn_wave_barrier();
       };
-      auto window_pre = [&](auto checked, int j) {
-          const uint64_t c = canon(j);
+      auto window_pre = [&](uint64_t c, bool valid) {
           const uint64_t z = mix3_head(c);
           const uint32_t ylo = (uint32_t)z * (uint32_t)kMixMul;
-          bool pass = ((ylo ^ (ylo >> 28)) & pmask) == kbits;
-          if constexpr (decltype(checked)::value) {
-            const bool valid = ((inv64 >> j) & wmask_bits) == 0;
-            win_count += valid ? 1u : 0u;
-            pass = pass && valid;
-          }
+          const bool pass = (((ylo ^ (ylo >> 28)) & pmask) == kbits) && valid;
           const uint64_t bal = __ballot(pass);
           const uint32_t below = __builtin_amdgcn_mbcnt_hi(
               (uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
@@ -474,13 +567,14 @@ __global__ __launch_bounds__(kBlock, SKS_SCAN_MIN_WAVES) void scan_kernel(ScanPa
             cnt = rest;
           }
       };
-      if (__all(lane_clean)) {
-#pragma unroll
-        for (int j = 0; j < kWPT; ++j) window_pre(std::false_type{}, j);
+      if (wave_clean) {
+        for_windows([&](int, uint64_t c) { window_pre(c, true); });
         win_count += kWPT;
-      } else {  // waves holding an invalid base: rare, kept out of the unrolled code
-#pragma unroll 1
-        for (int j = 0; j < kWPT; ++j) window_pre(std::true_type{}, j);
+      } else {
+        for_windows_checked([&](int, uint64_t c, bool valid) {
+          win_count += valid ? 1u : 0u;
+          window_pre(c, valid);
+        });
       }
       if (cnt) finish(cnt);
     } else {
@@ -500,25 +594,22 @@ __global__ __launch_bounds__(kBlock, SKS_SCAN_MIN_WAVES) void scan_kernel(ScanPa
         return keep_fmh<MODE>(p, fmh_narrow<FLAVOUR>(p, c), thresh);
       }
     };
-    if (__all(lane_clean)) {
-#pragma unroll
-      for (int j = 0; j < kWPT; ++j) keepmask |= (keep_window(canon(j)) ? 1u : 0u) << j;
+    if (wave_clean) {
+      for_windows([&](int m, uint64_t c) { keepmask |= (keep_window(c) ? 1u : 0u) << m; });
       win_count += kWPT;
-    } else {  // waves holding an invalid base: rare, kept out of the unrolled code
-#pragma unroll 1
-      for (int j = 0; j < kWPT; ++j) {
-        const bool valid = ((inv64 >> j) & wmask_bits) == 0;
+    } else {
+      for_windows_checked([&](int m, uint64_t c, bool valid) {
         win_count += valid ? 1u : 0u;
-        keepmask |= (keep_window(canon(j)) && valid ? 1u : 0u) << j;
-      }
+        keepmask |= (keep_window(c) && valid ? 1u : 0u) << m;
+      });
     }
     while (keepmask) {
       const uint32_t j = __builtin_ctz(keepmask);
       keepmask &= keepmask - 1;
       if constexpr (MODE == kModeList) {
-        emit<MODE>(p, q, g.seg, g.win0 + (uint64_t)(kWPT * tid) + j, 0);  // window start byte
+        emit<MODE>(p, q, g.seg, g.win0 + (uint64_t)(16 * (wbase + j) + r), 0);  // window start byte
       } else {
-        const uint64_t c = canon(j);
+        const uint64_t c = canon_at(j);
         // bottom-s: the candidate's fmh is recomputed after compaction
         // (launch_fmh_narrow) instead of here, where the whole wave would wait
         // on the ~45-VALU hash for the ~5% of lanes holding a candidate

@@ -3,9 +3,9 @@ bench line's roofline.valu).
 
 Compiles csrc/scan.hip for gfx950 with -save-temps (the Makefile's flags) in a
 temp dir, takes the scan_kernel<0, 0, 1> function (FracMinHash, flavour B,
-low-bits pre-filter: config 3), splits it into basic blocks and picks the block
-with the most VALU instructions — the clean-wave window loop (one window per
-lane per iteration).  Each VALU op is priced with the measured wave64 issue
+low-bits pre-filter: config 3), splits it into basic blocks and picks the
+steady-state block of the clean-wave window loop (one window per lane per
+block): the leanest of the blocks holding the hash's ten v_mad_u64_u32.  Each VALU op is priced with the measured wave64 issue
 cost per SIMD of profiles/r01/isa_rates_microbench.txt (cycles at 2.4 GHz):
 ops measured there take their own figure; an unmeasured op takes the figure
 of its encoding class (VOP3 / 64-bit / multiply ~4.2, VOP2 / VOP1 ~2.2).
@@ -84,7 +84,12 @@ def main(dst=None):
             fcur.append(t)
     blocks.append(cur)
     full.append(fcur)
-    hot_i = max(range(len(blocks)), key=lambda i: len(blocks[i]))
+    # the window blocks are the ones that hold the hash (the most 64-bit multiplies: 10
+    # v_mad_u64_u32); of those the leanest is the steady-state window (the first also
+    # holds the lane's setup).  Other blocks (the register pack) can hold more VALU.
+    def mads(i):
+        return sum(t.startswith("v_mad_u64_u32") for t in blocks[i])
+    hot_i = max(range(len(blocks)), key=lambda i: (mads(i), -len(blocks[i])))
     hot = blocks[hot_i]
     if os.environ.get("SKS_VALU_LISTING"):  # the hot block's whole instruction text
         open(os.environ["SKS_VALU_LISTING"], "w").write("\n".join(full[hot_i]) + "\n")
