@@ -664,8 +664,12 @@ __global__ __launch_bounds__(kSelB) void k_bottom_fused(uint64_t* __restrict__ r
     __syncthreads();
     if (bmax > kBkMax) {  // uniform: the keys are still in registers
       // the block sort takes blocked input: pads (~0) are the largest keys, so
-      // the striped arrangement sorts to the same result
-      FuseSort<ITEMS>().sort(k, sort_storage, 0, key_bits);
+      // the striped arrangement sorts to the same result.  The sorted bits
+      // include the one above the key: a key of all ones (a mask without a
+      // position pair p, w - 1 - p allows it) equals a pad in its key_bits and
+      // the stable sort would leave the pads, which lie between the keys in
+      // this arrangement, mixed with those keys below position n
+      FuseSort<ITEMS>().sort(k, sort_storage, 0, key_bits < 64 ? key_bits + 1 : 64);
     } else {
       uint32_t run = excl;
 #pragma unroll

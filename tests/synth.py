@@ -44,6 +44,30 @@ def bases(n, seed, mut_seed=0, mut_rate=0.0, pos_offset=0, chunk=1 << 24):
     return out
 
 
+def positions_mask(positions):
+    """A spaced-seed mask from window positions: both bits of each, 3 << 2p."""
+    m = 0
+    for p in positions:
+        m |= 3 << (2 * p)
+    return m
+
+
+def caller_masks():
+    """(name, w, mask): masks a caller may legally pass that the seeded generator
+    never makes — an empty high or low 64-bit word at w > 32, a single position,
+    regular combs (many runs of set bits).  The CPU cross-check of the expected
+    values (tests/test_oracle.py) and the GPU tests share this list."""
+    return [
+        ("w40_low_word_only", 40, positions_mask(p for p in range(32) if p not in (5, 17, 18))),
+        ("w40_high_word_only", 40, positions_mask([32, 33, 35, 38, 39])),
+        ("w64_position_63", 64, positions_mask([63])),
+        ("w64_every_third", 64, positions_mask(range(0, 64, 3))),
+        ("w48_odd_positions", 48, positions_mask(range(1, 48, 2))),
+        ("w32_even_positions", 32, positions_mask(range(0, 32, 2))),
+        ("w32_position_31", 32, positions_mask([31])),
+    ]
+
+
 def fasta_text(records, width=80):
     """records: list of (name, bytes) -> FASTA bytes with `width`-column lines."""
     parts = []

@@ -111,6 +111,28 @@ def test_refport_bottom_s_matches_oracle():
             assert np.array_equal(want, got), (w, k, s, flavour)
 
 
+@pytest.mark.parametrize("name,w,m", synth.caller_masks(), ids=[c[0] for c in synth.caller_masks()])
+def test_refport_matches_oracle_caller_masks(name, w, m):
+    """The hand-made masks of tests/test_scan_wide_layout.py (empty high or low
+    word, one position, combs): the oracle and the reference-style port agree on
+    FracMinHash c = 1 and bottom-s s = 500, both flavours, so the values the
+    GPU tests expect are cross-checked here without a GPU."""
+    assert m and m >> (2 * w) == 0
+    seq = synth.bases(9000, seed=17)
+    seq[4000] = ord("N")
+    runs = O.cut_runs(seq.tobytes())
+    codes = np.frombuffer(b"".join(runs), dtype=np.uint8)
+    lens = np.array([len(r) for r in runs], dtype=np.uint64)
+    for flavour in (0, 1):
+        want, nw = O.sketch(runs, w, m, "frac", 1, 1, flavour)
+        assert nw == sum(max(0, len(r) - w + 1) for r in runs)
+        got = O.refport_sketch_runs(runs, w, m, 1, 1, flavour).elems()
+        assert np.array_equal(want, got), (name, "frac", flavour)
+        want, _ = O.sketch(runs, w, m, "bottom", 500, 1, flavour)
+        got = O.refport_bottom_codes(codes, lens, w, m, 500, 1, flavour).elems()
+        assert np.array_equal(want, got), (name, "bottom", flavour)
+
+
 def test_refport_intersection_matches_merge():
     runs_a = O.cut_runs(synth.bases(30000, seed=21).tobytes())
     runs_b = O.cut_runs(synth.bases(30000, seed=21, mut_seed=5, mut_rate=0.01).tobytes())
