@@ -503,6 +503,30 @@ int sks_ctx_last_ingress_ms(sks_ctx* ctx, float* ms);
 int sks_ctx_last_intersect_ms(sks_ctx* ctx, float* ms);
 /* Fix the scan kernel's persistent grid size (0 = derive from occupancy). */
 int sks_ctx_set_scan_grid(sks_ctx* ctx, int grid);
+/* Post-processing of a build of ONE FracMinHash genome with window <= 32.  By
+ * default such a build takes the fused path when the expected survivors fit
+ * its buckets: the survivors are split by their top key bits into `buckets`
+ * regions of `bucket_capacity` keys, sorted and uniqued per bucket and gathered
+ * on the device, with one host round trip per build.  GENERAL forces the
+ * device-wide sort + unique every other build uses, FUSED takes the fused path
+ * even when the SKS_NO_FRAC_FUSED environment variable is set.  For tests,
+ * bucket_capacity and buckets (a power of two) lower the path's own choices
+ * (0: keep them; larger values are clamped): a bucket that receives more keys
+ * than its capacity is a status, after which the general post-processing runs
+ * on the same scan records.  Every path gives identical sketches. */
+enum {
+  SKS_FRAC_POST_AUTO = 0,
+  SKS_FRAC_POST_GENERAL = 1,
+  SKS_FRAC_POST_FUSED = 2
+};
+int sks_ctx_set_frac_post(sks_ctx* ctx, int mode, uint32_t bucket_capacity, uint32_t buckets);
+/* The path the context's last sks_sketch_build took (-1 for NULL). */
+enum {
+  SKS_BUILD_PATH_GENERAL = 0,
+  SKS_BUILD_PATH_FUSED = 1,                   /* fused FracMinHash post-processing */
+  SKS_BUILD_PATH_FUSED_THEN_GENERAL_POST = 2  /* its status was raised: general post-processing, same scan */
+};
+int sks_ctx_last_build_path(const sks_ctx* ctx);
 /* Kernel used by sks_intersect_all / sks_intersect_sym for u64 sketches.  All
  * give identical counts; AUTO (default) = the LDS hash join when the bucket
  * sizes allow it, else the LDS merge tiles, else one wavefront per pair.

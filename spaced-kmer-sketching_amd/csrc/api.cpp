@@ -214,6 +214,12 @@ struct sks_ctx {
   bool join_check = false;  // invariant-checking join / layout kernels (sks_ctx_set_join_check)
   uint32_t layout_blocks_hint = 0;  // sks_ctx_set_layout_blocks_hint (0: every block holds sketches)
   sks::Scratch root;                // sks_ctx_ani_table: ANI by shared-element count for one set size
+  sks::Scratch fstate;              // build_frac_single: bucket cursors, distinct counts, status
+  bool fstate_clean = false;        // fstate is zeroed and no launch sequence was cut short
+  int frac_mode = SKS_FRAC_POST_AUTO;  // sks_ctx_set_frac_post
+  uint32_t frac_bucket_cap = 0;     // 0: the kernel's capacity
+  uint32_t frac_buckets = 0;        // 0: chosen from the expected survivors
+  int last_path = SKS_BUILD_PATH_GENERAL;  // sks_ctx_last_build_path
   uint32_t root_size = 0;
   int root_k = 0;                   // 0: no table
 };
@@ -409,7 +415,7 @@ void release_set_arrays(sks_sketch_set* set, hipStream_t stream, bool ordered) {
   uint64_t total = 0;
   for (uint32_t v : set->sizes) total += v;
   void* arrays[3] = {set->d_data, set->d_starts, set->d_sizes};
-  const size_t bytes[3] = {std::max<uint64_t>(total * set->elem_words, 1) * 8,
+  const size_t bytes[3] = {std::max<size_t>(std::max<uint64_t>(total * set->elem_words, 1) * 8, set->data_bytes),
                            (size_t)std::max<uint32_t>(set->n, 1) * 8,
                            (size_t)std::max<uint32_t>(set->n, 1) * 4};
   for (int i = 0; i < 3; ++i) {
@@ -597,7 +603,7 @@ int sks_ctx_create(int device, void* stream, sks_ctx** out) {
   c->stream = reinterpret_cast<hipStream_t>(stream);
   // every scratch buffer is used on the context's stream only
   for (sks::Scratch* sc : {&c->ingress, &c->tmp, &c->rec[0], &c->rec[1], &c->rec[2], &c->flag,
-                           &c->pos, &c->meta, &c->iwork, &c->tdone, &c->lay, &c->root})
+                           &c->pos, &c->meta, &c->iwork, &c->tdone, &c->lay, &c->root, &c->fstate})
     sc->owner = &c->stream;
   for (auto& b : c->buf) b.owner = &c->stream;
   if (hipEventCreate(&c->ev_begin) != hipSuccess || hipEventCreate(&c->ev_end) != hipSuccess ||
@@ -634,6 +640,7 @@ int sks_ctx_destroy(sks_ctx* c) {
   c->tdone.release();
   c->lay.release();
   c->root.release();
+  c->fstate.release();
   c->ingress.release();
   trim_device_cache(c->device);
   (void)hipEventDestroy(c->ev_begin);
@@ -679,6 +686,19 @@ int sks_ctx_set_scan_grid(sks_ctx* c, int grid) {
   c->grid_override = grid;
   return SKS_OK;
 }
+
+int sks_ctx_set_frac_post(sks_ctx* c, int mode, uint32_t bucket_capacity, uint32_t buckets) {
+  if (!c) return sks::fail(SKS_E_ARG, "sks_ctx_set_frac_post: null ctx");
+  if (mode != SKS_FRAC_POST_AUTO && mode != SKS_FRAC_POST_GENERAL && mode != SKS_FRAC_POST_FUSED)
+    return sks::fail(SKS_E_ARG, "sks_ctx_set_frac_post: unknown mode");
+  if (buckets & (buckets - 1)) return sks::fail(SKS_E_ARG, "sks_ctx_set_frac_post: buckets must be a power of two");
+  c->frac_mode = mode;
+  c->frac_bucket_cap = bucket_capacity;
+  c->frac_buckets = buckets;
+  return SKS_OK;
+}
+
+int sks_ctx_last_build_path(const sks_ctx* c) { return c ? c->last_path : -1; }
 
 int sks_ctx_set_intersect_kernel(sks_ctx* c, int kind) {
   if (!c) return sks::fail(SKS_E_ARG, "null ctx");
@@ -1159,6 +1179,137 @@ int build_bottom_single(BuildState& S, const uint8_t* d_seq, const uint64_t* seg
   return SKS_OK;
 }
 
+// The bucket count (log2) the fused FracMinHash post-processing uses for a
+// record region of `cap` keys, or -1 when it does not apply.  The mean bucket
+// holds at most a quarter of a bucket's capacity: canonical k-mers (the smaller
+// of two strands) are twice as dense at the low end of the key range as on
+// average, which leaves a factor of two over the densest bucket.
+int frac_plan_log_b(const sks_ctx* c, uint64_t cap) {
+  const uint64_t per = sks::frac_bucket_capacity() / 4;
+  const uint64_t need = (std::max<uint64_t>(cap, 1) + per - 1) / per;
+  int lb = 0;
+  while ((1ull << lb) < need) ++lb;
+  if (lb > (int)sks::frac_max_log_buckets()) return -1;
+  if (c->frac_buckets) {  // test control: fewer buckets
+    int fb = 0;
+    while ((1u << fb) < c->frac_buckets) ++fb;
+    lb = std::min(lb, fb);
+  }
+  return lb;
+}
+
+constexpr int kFastPostFallback = -2;  // not an SKS status: the scan stands, take the general post_process
+
+// One narrow FracMinHash genome (the headline's shape): the scan, then a
+// bucketed sort + unique on the device (post.hip launch_frac_fused) that reads
+// the survivor count from device memory and writes the sketch set's own arrays;
+// one metadata upload, and one read-back of (survivors, windows, size, status)
+// at the end as the build's only host round trip — instead of a count
+// read-back, compaction, a device-wide radix sort, flags + scan + counts with a
+// second read-back, an allocation, a scatter and two uploads.  Returns
+// kFastFallback when the scan overflowed its record region (the general build
+// rescans with the counted capacity) and kFastPostFallback, with *survivors and
+// *windows set, when a bucket or sub-bucket capacity was short (the records
+// are intact: the general post_process runs on them without a second scan).
+int build_frac_single(BuildState& S, const uint8_t* d_seq, const uint64_t* seg_off, uint64_t cap, int log_b,
+                      sks_timings& tm, sks_sketch_set** out, uint64_t* survivors_out, uint64_t* windows_out) {
+  sks_ctx* c = S.c;
+  hipStream_t st = c->stream;
+  const uint64_t n_tiles = sks::scan_tiles_for(seg_off[1] - seg_off[0]);
+  const uint32_t bucket_cap = c->frac_bucket_cap
+                                  ? std::min<uint32_t>(c->frac_bucket_cap, sks::frac_bucket_capacity())
+                                  : sks::frac_bucket_capacity();
+  const uint64_t slots = std::max<uint64_t>(cap, 1);
+  SKS_HIP(c->rec[0].reserve(slots * sizeof(uint64_t)));
+  SKS_HIP(c->buf[0].reserve(((uint64_t)bucket_cap << log_b) * sizeof(uint64_t)));
+  SKS_HIP(c->fstate.reserve(sks::frac_state_bytes()));
+  if (!c->fstate_clean) SKS_HIP(hipMemsetAsync(c->fstate.ptr, 0, sks::frac_state_bytes(), st));
+  c->fstate_clean = false;  // until the whole sequence below is queued
+  MetaArena arena(c);
+  const size_t o_beg = arena.add({seg_off[0]}), o_end = arena.add({seg_off[1]}), o_tp = arena.add({0, n_tiles}),
+               o_thr = arena.add({~0ull}), o_cap = arena.add({cap}), o_off = arena.add({0}),
+               o_cnt = arena.add_zero(1), o_win = arena.add_zero(1), o_res = arena.add_zero(2),
+               o_queue = arena.add_zero(1);
+  if (o_win != o_cnt + 2 || o_res != o_win + 2) return sks::fail(SKS_E_HIP, "sks_sketch_build: arena layout");
+  SKS_TRY(arena.upload());
+  sks_sketch_set* set = new (std::nothrow) sks_sketch_set();
+  if (!set) return sks::fail(SKS_E_NOMEM, "sks_sketch_build: out of memory");
+  set->device = c->device;
+  set->n = 1;
+  // the record region's capacity bounds the survivors, hence the sketch
+  int rc = alloc_u64(&set->d_data, slots, &set->data_bytes);
+  if (rc == SKS_OK) rc = alloc_u64(&set->d_starts, 1);
+  if (rc == SKS_OK && dev_alloc(reinterpret_cast<void**>(&set->d_sizes), sizeof(uint32_t)) != hipSuccess)
+    rc = sks::fail(SKS_E_HIP, "sks_sketch_build: device allocation failed");
+  auto drop = [&]() {  // arrays still unused by the device or idle after a sync
+    dev_release(set->d_data, set->data_bytes);
+    dev_release(set->d_starts, 8);
+    dev_release(set->d_sizes, 8);
+    delete set;
+  };
+  if (rc != SKS_OK) {
+    drop();
+    return rc;
+  }
+  const sks::ScanParams p =
+      scan_params(S, d_seq, arena, o_beg, o_end, o_tp, o_thr, o_cap, o_off, o_cnt, o_win, 1, n_tiles, o_queue);
+  const sks::BitRuns runs = sks::bit_runs(S.mask_lo);
+  const int kb = std::max(1, __builtin_popcountll(S.mask_lo));
+  hipError_t e = hipEventRecord(c->ev_s0, st);
+  if (e == hipSuccess) e = sks::launch_scan(p, sks::kModeFrac, S.pol.flavour, false, c->device, st, c->grid_override);
+  if (e == hipSuccess) e = hipEventRecord(c->ev_s1, st);
+  if (e == hipSuccess)
+    e = sks::launch_frac_fused(reinterpret_cast<uint64_t*>(c->rec[0].ptr), arena.ptr(o_cnt), arena.ptr(o_cap), slots,
+                               kb, runs, (uint32_t)log_b, bucket_cap, col(c, 0),
+                               reinterpret_cast<uint32_t*>(c->fstate.ptr), set->d_data, set->d_sizes, set->d_starts,
+                               arena.ptr(o_res), st);
+  if (e == hipSuccess) {
+    c->fstate_clean = true;
+    e = hipEventRecord(c->ev_end, st);
+  }
+  uint64_t h[6] = {0, 0, 0, 0, 0, 0};  // survivors, -, windows, -, size, status
+  if (e == hipSuccess) e = sks::pinned_d2h(h, arena.ptr(o_cnt), sizeof h, st);  // synchronises the stream
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    c->fstate_clean = false;
+    drop();
+    return sks::fail(SKS_E_HIP, std::string("sks_sketch_build: ") + hipGetErrorString(e));
+  }
+  const uint64_t survivors = h[0], windows = h[2], size = h[4], status = h[5];
+  float ms = 0, tot = 0;
+  (void)hipEventElapsedTime(&ms, c->ev_s0, c->ev_s1);
+  (void)hipEventElapsedTime(&tot, c->ev_begin, c->ev_end);
+  tm.scan_ms = ms;
+  tm.scan_launches = n_tiles ? 1 : 0;
+  tm.survivors = survivors;
+  if (survivors > cap || size > survivors) {  // the scan dropped records: rescan with the counted capacity
+    drop();
+    *survivors_out = survivors;
+    return kFastFallback;
+  }
+  if (status != 0) {
+    drop();
+    *survivors_out = survivors;
+    *windows_out = windows;
+    return kFastPostFallback;
+  }
+  tm.windows = windows;
+  tm.total_ms = tot;
+  tm.post_ms = tot - ms;
+  set->elem_words = 1;
+  set->sizes = {(uint32_t)size};
+  set->starts = {0};
+  set->windows = {windows};
+  set->window = S.w;
+  set->mask[0] = S.mask_lo;
+  set->mask[1] = S.mask_hi;
+  set->policy = S.pol;
+  c->last = tm;
+  c->last_path = SKS_BUILD_PATH_FUSED;
+  *out = set;
+  return SKS_OK;
+}
+
 // Argument checks shared by sks_sketch_build and sks_kmer_list_build.
 int validate_build(const char* fn, sks_ctx* c, const uint8_t* d_seq, uint64_t n_bytes,
                    const uint64_t* seg_off, uint32_t n_seg, int window, const uint64_t mask[2],
@@ -1212,6 +1363,7 @@ int sks_sketch_build(sks_ctx* c, const uint8_t* d_seq, uint64_t n_bytes, const u
   const double alpha = 1.0 + 10.0 / std::sqrt((double)policy->param) + 1.0 / (double)policy->param;
 
   sks_timings tm{};
+  c->last_path = SKS_BUILD_PATH_GENERAL;
   SKS_HIP(hipEventRecord(c->ev_begin, st));
 
   std::vector<uint64_t> thresh_g(n_seg, ~0ull), cap_g(n_seg), windows_g(n_seg, 0);
@@ -1251,6 +1403,28 @@ int sks_sketch_build(sks_ctx* c, const uint8_t* d_seq, uint64_t n_bytes, const u
     }
   }
 
+  // one narrow FracMinHash genome: the single-round-trip path when the expected
+  // survivors fit its buckets.  prescan: its scan's records stand (region 0 at
+  // offset 0 with capacity cap_g[0], as the first pass below would lay it out)
+  // and only the general post-processing is still to run
+  bool prescan = false;
+  uint64_t pre_survivors = 0, pre_windows = 0;
+  if (!bottom && !S.wide && n_seg == 1 && c->frac_mode != SKS_FRAC_POST_GENERAL &&
+      (c->frac_mode == SKS_FRAC_POST_FUSED || getenv("SKS_NO_FRAC_FUSED") == nullptr)) {
+    const int log_b = frac_plan_log_b(c, cap_g[0]);
+    if (log_b >= 0) {
+      const int rc = build_frac_single(S, d_seq, seg_off, cap_g[0], log_b, tm, out, &pre_survivors, &pre_windows);
+      if (rc == kFastPostFallback) {
+        prescan = true;
+        c->last_path = SKS_BUILD_PATH_FUSED_THEN_GENERAL_POST;
+      } else if (rc != kFastFallback) {
+        return rc;
+      } else {
+        cap_g[0] = std::max(cap_g[0], pre_survivors);  // the general build's first scan then fits
+      }
+    }
+  }
+
   std::vector<PassOut> passes;
   std::vector<uint32_t> pending(n_seg);
   std::iota(pending.begin(), pending.end(), 0);
@@ -1274,30 +1448,40 @@ int sks_sketch_build(sks_ctx* c, const uint8_t* d_seq, uint64_t n_bytes, const u
       total_cap += cap[i];
     }
     const uint64_t n_tiles = tp[m];
-    for (int r = 0; r < (bottom && S.wide ? 3 : (bottom || S.wide ? 2 : 1)); ++r)
-      SKS_HIP(c->rec[r].reserve(std::max<uint64_t>(total_cap, 1) * sizeof(uint64_t)));
-    MetaArena arena(c);
-    size_t o_beg = arena.add(beg), o_end = arena.add(end), o_tp = arena.add(tp),
-           o_thr = arena.add(thr), o_cap = arena.add(cap), o_off = arena.add(ooff),
-           o_cnt = arena.add_zero(m), o_win = arena.add_zero(m), o_queue = arena.add_zero(1);
-    SKS_TRY(arena.upload());
+    std::vector<uint64_t> counts, wins;
+    if (prescan) {
+      // build_frac_single's scan: its time and launch are in tm already
+      prescan = false;
+      counts = {pre_survivors};
+      wins = {pre_windows};
+      tm.survivors = 0;  // added below
+    } else {
+      for (int r = 0; r < (bottom && S.wide ? 3 : (bottom || S.wide ? 2 : 1)); ++r)
+        SKS_HIP(c->rec[r].reserve(std::max<uint64_t>(total_cap, 1) * sizeof(uint64_t)));
+      MetaArena arena(c);
+      size_t o_beg = arena.add(beg), o_end = arena.add(end), o_tp = arena.add(tp),
+             o_thr = arena.add(thr), o_cap = arena.add(cap), o_off = arena.add(ooff),
+             o_cnt = arena.add_zero(m), o_win = arena.add_zero(m), o_queue = arena.add_zero(1);
+      SKS_TRY(arena.upload());
 
-    const sks::ScanParams p = scan_params(S, d_seq, arena, o_beg, o_end, o_tp, o_thr, o_cap, o_off, o_cnt, o_win,
-                                          m, n_tiles, o_queue);
+      const sks::ScanParams p = scan_params(S, d_seq, arena, o_beg, o_end, o_tp, o_thr, o_cap, o_off, o_cnt, o_win,
+                                            m, n_tiles, o_queue);
 
-    SKS_HIP(hipEventRecord(c->ev_s0, st));
-    SKS_HIP(sks::launch_scan(p, bottom ? sks::kModeBottom : sks::kModeFrac, policy->flavour,
-                             S.wide, c->device, st, c->grid_override));
-    SKS_HIP(hipEventRecord(c->ev_s1, st));
-    tm.scan_launches += n_tiles ? 1 : 0;
-    // survivor and window counts sit next to each other in the arena: one read-back
-    if (o_win != o_cnt + m + 1) return sks::fail(SKS_E_HIP, "sks_sketch_build: arena layout");
-    std::vector<uint64_t> cw(2 * (m + 1));
-    SKS_HIP(sks::pinned_d2h(cw.data(), arena.ptr(o_cnt), cw.size() * sizeof(uint64_t), st));
-    std::vector<uint64_t> counts(cw.begin(), cw.begin() + m), wins(cw.begin() + (m + 1), cw.begin() + (m + 1) + m);
-    float ms = 0;
-    SKS_HIP(hipEventElapsedTime(&ms, c->ev_s0, c->ev_s1));
-    tm.scan_ms += ms;
+      SKS_HIP(hipEventRecord(c->ev_s0, st));
+      SKS_HIP(sks::launch_scan(p, bottom ? sks::kModeBottom : sks::kModeFrac, policy->flavour,
+                               S.wide, c->device, st, c->grid_override));
+      SKS_HIP(hipEventRecord(c->ev_s1, st));
+      tm.scan_launches += n_tiles ? 1 : 0;
+      // survivor and window counts sit next to each other in the arena: one read-back
+      if (o_win != o_cnt + m + 1) return sks::fail(SKS_E_HIP, "sks_sketch_build: arena layout");
+      std::vector<uint64_t> cw(2 * (m + 1));
+      SKS_HIP(sks::pinned_d2h(cw.data(), arena.ptr(o_cnt), cw.size() * sizeof(uint64_t), st));
+      counts.assign(cw.begin(), cw.begin() + m);
+      wins.assign(cw.begin() + (m + 1), cw.begin() + (m + 1) + m);
+      float ms = 0;
+      SKS_HIP(hipEventElapsedTime(&ms, c->ev_s0, c->ev_s1));
+      tm.scan_ms += ms;
+    }
 
     std::vector<uint32_t> ok, next;
     for (uint32_t i = 0; i < m; ++i) {

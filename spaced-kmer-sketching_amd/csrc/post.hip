@@ -797,6 +797,272 @@ __global__ __launch_bounds__(kSelB) void k_bottom_fused(uint64_t* __restrict__ r
   FSTAMP(7);
 }
 
+// ---- FracMinHash of one narrow genome: bucketed sort + unique ---------------------------
+// Three launches behind the scan, none of which needs a count on the host
+// (launch_frac_fused).  The packed keys are split by their top bits into
+// n_buckets disjoint key ranges, so bucket order is global order and a
+// duplicate never spans buckets; each bucket is then sorted and uniqued by one
+// workgroup in LDS, and the buckets' distinct keys are copied to their final
+// place.  Every capacity is checked before a write: a bucket over its capacity
+// or keys crowding one sub-bucket raise a status bit, and the host runs the
+// general post-processing on the (untouched) scan records instead.
+constexpr int kFracB = 256;
+constexpr int kFracWaves = kFracB / 64;
+constexpr uint32_t kFracItems = 16;
+constexpr uint32_t kFracCap = kFracB * kFracItems;  // 4096 keys: one bucket, 32 KB of LDS
+constexpr int kFracPartB = 1024;                    // partition workgroup
+constexpr uint32_t kFracPartTile = 1u << 14;        // records per partition workgroup (sizes its grid, <= 256)
+constexpr int kFracSubLog = 11;
+constexpr uint32_t kFracSub = 1u << kFracSubLog;    // counting-sort sub-buckets per bucket
+constexpr uint32_t kFracSubPer = kFracSub / kFracB;
+constexpr uint32_t kFracSubMax = 32;                // keys one thread insertion-sorts in a sub-bucket
+constexpr uint32_t kFracMaxLogB = 14;
+// state words (uint32): [0, 2^14) bucket cursors, [2^14, 2^15) distinct counts, then the status
+constexpr uint32_t kFracStateCounts = 1u << kFracMaxLogB;
+constexpr uint32_t kFracStateStatus = 2u << kFracMaxLogB;
+
+// Each workgroup takes one contiguous share of the records, counts its keys
+// per bucket in LDS, reserves a range of each bucket's region with ONE global
+// atomic per (workgroup, bucket), and places its keys from a second read of its
+// share (L2) with LDS atomics.  One global atomic per key took 360 us for
+// config 3's 3.0 M keys on 4096 cursors; this takes ~60 us at 8 k - 16 k records
+// per workgroup (two dependent passes of loads per workgroup: 126 us at 64 k
+// records, 47 workgroups; below 8 k the reservations approach one per key again).
+// The cursors are zero on entry (state is zeroed when allocated, and
+// k_frac_sort_unique zeroes each cursor as it reads it).  A scan that counted
+// more records than its region holds leaves everything empty: the host rescans.
+__global__ __launch_bounds__(kFracPartB) void k_frac_partition(const uint64_t* __restrict__ rec,
+                                                               const uint64_t* __restrict__ seg_count,
+                                                               const uint64_t* __restrict__ seg_cap,
+                                                               const BitRuns runs, int shift, uint32_t n_buckets,
+                                                               uint32_t bucket_cap, uint64_t* __restrict__ regions,
+                                                               uint32_t* __restrict__ state) {
+  extern __shared__ uint32_t s_cur[];  // [n_buckets] counts, then this workgroup's cursors
+  const uint64_t n = seg_count[0];
+  if (n > seg_cap[0]) return;
+  // shares of whole 1024-record rows, so every workgroup's loads are aligned
+  const uint64_t rows = (n + kFracPartB - 1) / kFracPartB;
+  const uint64_t share = (rows + gridDim.x - 1) / gridDim.x * kFracPartB;
+  const uint64_t lo = min((uint64_t)blockIdx.x * share, n), hi = min(lo + share, n);
+  if (lo >= hi) return;  // uniform
+  // packed keys fit shift + log2(n_buckets) bits; the clamp keeps any other key in range
+  auto bucket_of = [&](uint64_t key) {
+    const uint64_t top = shift < 64 ? key >> shift : 0ull;
+    return (uint32_t)min(top, (uint64_t)(n_buckets - 1));
+  };
+  for (uint32_t b = threadIdx.x; b < n_buckets; b += kFracPartB) s_cur[b] = 0;
+  __syncthreads();
+#pragma unroll 4
+  for (uint64_t i = lo + threadIdx.x; i < hi; i += kFracPartB) atomicAdd(&s_cur[bucket_of(runs_pack(rec[i], runs))], 1u);
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < n_buckets; b += kFracPartB) {
+    const uint32_t c = s_cur[b];
+    if (c) s_cur[b] = atomicAdd(&state[b], c);
+  }
+  __syncthreads();
+  bool over = false;
+#pragma unroll 4
+  for (uint64_t i = lo + threadIdx.x; i < hi; i += kFracPartB) {
+    const uint64_t key = runs_pack(rec[i], runs);
+    const uint32_t b = bucket_of(key);
+    const uint32_t slot = atomicAdd(&s_cur[b], 1u);
+    if (slot < bucket_cap) regions[(uint64_t)b * bucket_cap + slot] = key;
+    else over = true;
+  }
+  if (over) atomicOr(&state[kFracStateStatus], (uint32_t)kFracStatusBucket);
+}
+
+// exclusive block scan of one count per thread, *total = the sum (wsum: kFracWaves words)
+__device__ __forceinline__ uint32_t frac_excl_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t t = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += t;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  uint32_t before = inc - v, all = 0;
+#pragma unroll
+  for (int w = 0; w < kFracWaves; ++w) {
+    before += w < wave ? wsum[w] : 0u;
+    all += wsum[w];
+  }
+  __syncthreads();
+  *total = all;
+  return before;
+}
+
+// The sort and unique of one bucket's n keys at reg[0 .. n), n <= ITEMS * kFracB.
+template <uint32_t ITEMS>
+__device__ __forceinline__ void frac_sort_body(uint64_t* __restrict__ reg, uint32_t n, uint32_t b,
+                                               uint32_t* __restrict__ state, const BitRuns& runs, int shift,
+                                               uint64_t* skeys, uint32_t* sbin, uint32_t* wsum, uint32_t* wmax) {
+  const int tid = threadIdx.x;
+  uint64_t k[ITEMS];
+#pragma unroll
+  for (uint32_t j = 0; j < ITEMS; ++j) {
+    const uint32_t i = j * kFracB + tid;
+    k[j] = i < n ? reg[i] : ~0ull;
+  }
+  // the bucket's keys agree above `shift`; sub-bucket = the next kFracSubLog bits
+  // (all of the low bits when there are fewer), which keeps the key order
+  const uint64_t low = shift >= 64 ? ~0ull : (1ull << shift) - 1;
+  const int sub_shift = shift > kFracSubLog ? shift - kFracSubLog : 0;
+  auto sub_of = [&](uint64_t key) { return (uint32_t)min((key & low) >> sub_shift, (uint64_t)(kFracSub - 1)); };
+#pragma unroll
+  for (uint32_t j = 0; j < ITEMS; ++j)
+    if (j * kFracB + tid < n) atomicAdd(&sbin[sub_of(k[j])], 1u);
+  __syncthreads();
+  uint32_t cb[kFracSubPer], sum = 0, mx = 0;
+#pragma unroll
+  for (uint32_t q = 0; q < kFracSubPer; ++q) {
+    cb[q] = sbin[tid * kFracSubPer + q];
+    sum += cb[q];
+    mx = cb[q] > mx ? cb[q] : mx;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor(mx, o, 64));
+  if ((tid & 63) == 0) wmax[tid >> 6] = mx;
+  uint32_t total;
+  const uint32_t excl = frac_excl_scan(sum, wsum, &total);  // its barriers publish wmax
+  uint32_t bmax = 0;
+#pragma unroll
+  for (int w = 0; w < kFracWaves; ++w) bmax = wmax[w] > bmax ? wmax[w] : bmax;
+  if (bmax > kFracSubMax) {  // uniform: keys crowd a sub-bucket (low-complexity sequence, a short mask)
+    if (tid == 0) {
+      state[kFracStateCounts + b] = 0;
+      atomicOr(&state[kFracStateStatus], (uint32_t)kFracStatusCrowd);
+    }
+    return;
+  }
+  {
+    uint32_t run = excl;
+#pragma unroll
+    for (uint32_t q = 0; q < kFracSubPer; ++q) {  // sub-bucket cursors
+      sbin[tid * kFracSubPer + q] = run;
+      run += cb[q];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t j = 0; j < ITEMS; ++j)
+    if (j * kFracB + tid < n) skeys[atomicAdd(&sbin[sub_of(k[j])], 1u)] = k[j];
+  __syncthreads();
+  {
+    uint32_t st = excl;  // this thread's sub-buckets are the contiguous range [excl, excl + sum)
+#pragma unroll 1
+    for (uint32_t q = 0; q < kFracSubPer; ++q) {
+      const uint32_t c = cb[q];
+      for (uint32_t i = 1; i < c; ++i) {
+        const uint64_t key = skeys[st + i];
+        uint32_t j = i;
+        while (j > 0 && skeys[st + j - 1] > key) {
+          skeys[st + j] = skeys[st + j - 1];
+          --j;
+        }
+        skeys[st + j] = key;
+      }
+      st += c;
+    }
+  }
+  __syncthreads();
+  // blocked order from here: thread t holds the sorted positions t * ITEMS ..
+  const uint64_t before = tid ? skeys[tid * ITEMS - 1] : 0ull;
+  uint32_t first_m = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < ITEMS; ++j) {
+    const uint32_t i = tid * ITEMS + j;
+    k[j] = skeys[i];
+    const bool first = i < n && (i == 0 || k[j] != (j ? k[j - 1] : before));
+    first_m |= (first ? 1u : 0u) << j;
+  }
+  uint32_t distinct;
+  uint32_t pos = frac_excl_scan((uint32_t)__builtin_popcount(first_m), wsum, &distinct);  // barriers: reads done
+#pragma unroll
+  for (uint32_t j = 0; j < ITEMS; ++j)
+    if ((first_m >> j) & 1u) skeys[pos++] = k[j];
+  __syncthreads();
+  for (uint32_t i = tid; i < distinct; i += kFracB) reg[i] = runs_expand(skeys[i], runs);
+  if (tid == 0) state[kFracStateCounts + b] = distinct;
+}
+
+// One workgroup per bucket: a counting sort on the kFracSubLog bits below the
+// bucket bits (k_bottom_fused's scheme at a quarter of its size: a bucket holds
+// ~0.2-0.7 keys per sub-bucket), an insertion sort of each thread's
+// sub-buckets in LDS, first-of-run flags, a block scan, and the distinct keys
+// written back over the bucket's own region, expanded to their mask bits.
+__global__ __launch_bounds__(kFracB) void k_frac_sort_unique(uint64_t* __restrict__ regions,
+                                                             uint32_t* __restrict__ state, const BitRuns runs,
+                                                             int shift, uint32_t bucket_cap) {
+  __shared__ uint64_t skeys[kFracCap];
+  __shared__ uint32_t sbin[kFracSub];
+  __shared__ uint32_t wsum[kFracWaves], wmax[kFracWaves];
+  __shared__ uint32_t s_n;
+  const uint32_t b = blockIdx.x;
+  const int tid = threadIdx.x;
+  uint32_t* counts = state + kFracStateCounts;
+  if (tid == 0) {
+    s_n = state[b];
+    state[b] = 0;  // the next build's partition finds its cursor zeroed
+  }
+#pragma unroll
+  for (uint32_t q = 0; q < kFracSubPer; ++q) sbin[tid * kFracSubPer + q] = 0;
+  __syncthreads();
+  const uint32_t n = s_n;
+  if (n == 0 || n > bucket_cap) {  // uniform; over capacity: only bucket_cap keys were written
+    if (tid == 0) {
+      counts[b] = 0;
+      if (n) atomicOr(&state[kFracStateStatus], (uint32_t)kFracStatusBucket);
+    }
+    return;
+  }
+  // bucket_cap <= kFracCap (host-checked); the register tile is the smallest that
+  // holds the bucket (a mean bucket is a fifth of the capacity)
+  uint64_t* reg = regions + (uint64_t)b * bucket_cap;
+  if (n <= 4 * kFracB) frac_sort_body<4>(reg, n, b, state, runs, shift, skeys, sbin, wsum, wmax);
+  else if (n <= 8 * kFracB) frac_sort_body<8>(reg, n, b, state, runs, shift, skeys, sbin, wsum, wmax);
+  else frac_sort_body<kFracItems>(reg, n, b, state, runs, shift, skeys, sbin, wsum, wmax);
+}
+
+// Bucket b's distinct keys to out[sum of the counts before b ..): every
+// workgroup recomputes its prefix (at most 2^14 counts).  The last bucket's
+// workgroup writes the set's size and start, the result words (distinct size,
+// status) and clears the status for the next build.
+__global__ __launch_bounds__(kFracB) void k_frac_gather(const uint64_t* __restrict__ regions,
+                                                        uint32_t* __restrict__ state, uint32_t n_buckets,
+                                                        uint32_t bucket_cap, uint64_t out_cap,
+                                                        uint64_t* __restrict__ out, uint32_t* __restrict__ set_sizes,
+                                                        uint64_t* __restrict__ set_starts,
+                                                        uint64_t* __restrict__ res) {
+  __shared__ uint32_t wsum[kFracWaves];
+  const uint32_t b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const uint32_t* counts = state + kFracStateCounts;
+  uint32_t part = 0;  // the counts sum to at most the survivors, below 2^32
+  for (uint32_t j = tid; j < b; j += kFracB) part += counts[j];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+  if ((tid & 63) == 0) wsum[tid >> 6] = part;
+  __syncthreads();
+  uint64_t prefix = 0;
+#pragma unroll
+  for (int w = 0; w < kFracWaves; ++w) prefix += wsum[w];
+  const uint32_t cnt = counts[b];
+  const uint64_t* reg = regions + (uint64_t)b * bucket_cap;
+  for (uint32_t i = tid; i < cnt; i += kFracB)
+    if (prefix + i < out_cap) out[prefix + i] = reg[i];
+  if (b == n_buckets - 1 && tid == 0) {
+    const uint64_t total = prefix + cnt;
+    set_sizes[0] = (uint32_t)total;
+    set_starts[0] = 0;
+    res[0] = total;
+    res[1] = state[kFracStateStatus];
+    state[kFracStateStatus] = 0;
+  }
+}
+
 template <int FLAVOUR>
 __global__ void k_fmh_narrow(uint64_t* __restrict__ keys, uint64_t n, uint64_t kconst) {
   const uint64_t i = (uint64_t)blockIdx.x * kB + threadIdx.x;
@@ -1070,6 +1336,29 @@ hipError_t launch_bottom_fused(uint64_t* rec, const uint64_t* d_src_off, const u
     return flavour == 0 ? go(k_bottom_fused<0, 12>, fuse_lds<12>())
                         : go(k_bottom_fused<1, 12>, fuse_lds<12>());
   return flavour == 0 ? go(k_bottom_fused<0, 16>, fuse_lds<16>()) : go(k_bottom_fused<1, 16>, fuse_lds<16>());
+}
+
+uint32_t frac_bucket_capacity() { return kFracCap; }
+uint32_t frac_max_log_buckets() { return kFracMaxLogB; }
+size_t frac_state_bytes() { return (size_t)(kFracStateStatus + 2) * sizeof(uint32_t); }
+
+hipError_t launch_frac_fused(const uint64_t* rec, const uint64_t* d_cnt, const uint64_t* d_cap, uint64_t cap,
+                             int key_bits, const BitRuns& runs, uint32_t log_b, uint32_t bucket_cap,
+                             uint64_t* regions, uint32_t* state, uint64_t* out, uint32_t* set_sizes,
+                             uint64_t* set_starts, uint64_t* d_res, hipStream_t s) {
+  if (log_b > kFracMaxLogB || bucket_cap == 0 || bucket_cap > kFracCap || key_bits < 1 || key_bits > 64)
+    return hipErrorInvalidValue;
+  const uint32_t n_buckets = 1u << log_b;
+  const int shift = key_bits > (int)log_b ? key_bits - (int)log_b : 0;
+  const uint64_t tiles = (std::max<uint64_t>(cap, 1) + kFracPartTile - 1) / kFracPartTile;
+  hipLaunchKernelGGL(k_frac_partition, dim3((unsigned)std::min<uint64_t>(tiles, 256)), dim3(kFracPartB),
+                     n_buckets * sizeof(uint32_t), s, rec, d_cnt, d_cap, runs, shift, n_buckets, bucket_cap, regions,
+                     state);
+  hipLaunchKernelGGL(k_frac_sort_unique, dim3(n_buckets), dim3(kFracB), 0, s, regions, state, runs, shift,
+                     bucket_cap);
+  hipLaunchKernelGGL(k_frac_gather, dim3(n_buckets), dim3(kFracB), 0, s, regions, state, n_buckets, bucket_cap,
+                     cap, out, set_sizes, set_starts, d_res);
+  return hipGetLastError();
 }
 
 hipError_t launch_iota(uint64_t* out, uint64_t n, hipStream_t s) {

@@ -14,6 +14,7 @@ struct sks_sketch_set {
   uint64_t* d_data = nullptr;    // elements (elem_words u64 each)
   uint64_t* d_starts = nullptr;  // [n] element index of each sketch
   uint32_t* d_sizes = nullptr;   // [n]
+  size_t data_bytes = 0;         // d_data's allocation when it is larger than the sketches (0: exact)
   std::vector<uint32_t> sizes;
   std::vector<uint64_t> starts;
   std::vector<uint64_t> windows;

@@ -121,6 +121,27 @@ hipError_t launch_bottom_fused(uint64_t* rec, const uint64_t* d_src_off, const u
                                uint64_t* d_res, hipStream_t s, const uint64_t* d_cap = nullptr,
                                uint32_t* set_sizes = nullptr, uint64_t* set_starts = nullptr);
 
+// FracMinHash post-processing of one narrow genome without a host round trip
+// (post.hip k_frac_partition / k_frac_sort_unique / k_frac_gather): the
+// d_cnt[0] <= d_cap[0] records at rec[0 ..) are packed, split by their top
+// log_b bits into 2^log_b regions of bucket_cap keys (regions: 2^log_b *
+// bucket_cap words), sorted and uniqued per bucket, and the distinct keys
+// written to out[0 ..) (capacity `cap` >= d_cap[0]) with set_sizes[0],
+// set_starts[0] and d_res = {distinct size, status}.  A non-zero status
+// (kFracStatus*) means a capacity was short and `out` is not the sketch; the
+// records are untouched.  d_cnt[0] > d_cap[0] yields size 0, status 0.
+// state: frac_state_bytes() of device words, zeroed once by the caller and left
+// zeroed (cursors, status) by every complete launch.
+constexpr uint64_t kFracStatusBucket = 1;  // a bucket received more than bucket_cap keys
+constexpr uint64_t kFracStatusCrowd = 2;   // keys crowd one sub-bucket of a bucket's sort
+uint32_t frac_bucket_capacity();           // keys one bucket's workgroup sorts (largest bucket_cap)
+uint32_t frac_max_log_buckets();           // largest log_b
+size_t frac_state_bytes();
+hipError_t launch_frac_fused(const uint64_t* rec, const uint64_t* d_cnt, const uint64_t* d_cap, uint64_t cap,
+                             int key_bits, const BitRuns& runs, uint32_t log_b, uint32_t bucket_cap,
+                             uint64_t* regions, uint32_t* state, uint64_t* out, uint32_t* set_sizes,
+                             uint64_t* set_starts, uint64_t* d_res, hipStream_t s);
+
 // Compact sparse survivor regions [off[g], off[g] + cnt[g]) into dense CSR,
 // packing each value's mask bits when `pack` is given.  tag_shift >= 0 ORs the
 // segment index in above the key bits, (g << tag_shift) | key: the segments of a

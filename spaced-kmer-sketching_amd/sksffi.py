@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("SKS_LIB") or os.path.join(PKG_DIR, "lib", "libsks.so"
 SKS_FRAC_MOD = 0
 SKS_BOTTOM_S = 1
 INTERSECT_AUTO, INTERSECT_MERGE, INTERSECT_JOIN, INTERSECT_GLOBAL = 0, 1, 2, 3
+FRAC_POST_AUTO, FRAC_POST_GENERAL, FRAC_POST_FUSED = 0, 1, 2
+BUILD_PATH_GENERAL, BUILD_PATH_FUSED, BUILD_PATH_FUSED_THEN_GENERAL_POST = 0, 1, 2
 FLAVOUR_BOOST_MIX = 0
 FLAVOUR_BOOST_LEGACY = 1
 
@@ -71,6 +73,7 @@ EXPORTED = [
     "sks_intersect_layout_ani", "sks_host_alloc", "sks_host_free", "sks_join_layout_stat_copy",
     "sks_sketches_export", "sks_all_pairs_ani", "sks_windows_dense", "sks_windows_dense_row_words",
     "sks_join_layout_bounds_for_mask", "sks_layout_tiles_ani",
+    "sks_ctx_set_frac_post", "sks_ctx_last_build_path",
 ]
 
 _lib = None
@@ -123,6 +126,8 @@ def lib():
     L.sks_ctx_last_timings.argtypes = [vp, C.POINTER(Timings)]
     L.sks_ctx_set_scan_grid.argtypes = [vp, C.c_int]
     L.sks_ctx_set_intersect_kernel.argtypes = [vp, C.c_int]
+    L.sks_ctx_set_frac_post.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32]
+    L.sks_ctx_last_build_path.argtypes = [vp]
     L.sks_sketch_union.argtypes = [vp, vp, C.c_uint64, vp, u64p]
     L.sks_sketch_union_wide.argtypes = [vp, vp, C.c_uint64, vp, u64p]
     L.sks_join_layout_log_b.argtypes = [C.c_uint32]
@@ -383,6 +388,15 @@ class Context:
 
     def set_scan_grid(self, grid):
         check(lib().sks_ctx_set_scan_grid(self.h, grid))
+
+    def set_frac_post(self, mode=0, bucket_capacity=0, buckets=0):
+        """sks_ctx_set_frac_post: FRAC_POST_AUTO / _GENERAL / _FUSED, and (tests)
+        a lower bucket capacity and bucket count for the fused path."""
+        check(lib().sks_ctx_set_frac_post(self.h, mode, bucket_capacity, buckets))
+
+    def last_build_path(self):
+        """BUILD_PATH_* of the context's last sketch_build."""
+        return int(lib().sks_ctx_last_build_path(self.h))
 
     def sketch_union(self, d_in, n, d_out, elem_words=1):
         """sks_sketch_union (elem_words 1: u64 values) or sks_sketch_union_wide
