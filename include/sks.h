@@ -440,6 +440,55 @@ int sks_layout_tiles_ani(sks_ctx* ctx, const uint64_t* d_data, const uint64_t* d
                          uint32_t blocks_hint, uint32_t blk0, const uint32_t* d_tiles, uint64_t n_tiles,
                          uint32_t n_global, const int32_t* d_sizes_global, int kmer_num_ones, double* ani,
                          int32_t* d_counts, uint32_t* d_status);
+/* ---- query-vs-reference search (no reference equivalent) -------------------------------
+ * "Which of these stored sketches contain my queries?": every query sketch
+ * against every reference sketch, with only the pairs that pass the thresholds
+ * coming back, as a compact list instead of a dense matrix.  The query set's
+ * join layout is built once (context scratch); the references are taken in
+ * batches of whole 64-sketch blocks, each batch's layout built with the query
+ * layout's log_b and group bounds and joined with it into packed count tiles
+ * (scratch), which a filter kernel turns into hit records on the device.
+ * Scratch is bounded by the query layout, one batch's layout and tiles, and
+ * the hit buffers, whatever the size of the reference set. */
+typedef struct sks_hit {       /* 32 bytes */
+  uint32_t query, ref;         /* indices into the two sets                       */
+  int32_t  shared;             /* |Q_query ∩ R_ref|                               */
+  int32_t  query_size;         /* |Q_query|                                       */
+  double   containment;        /* containment(shared, query_size)                 */
+  double   ani;                /* binomial_estimator(containment, kmer_num_ones)  */
+} sks_hit;
+/* Device-array form: queries (d_q_*) and references (d_r_*) as in the
+ * intersection entry points, with n sketches, the largest sketch (max_size) and
+ * the sizes' sum (total, or an upper bound) of each side.  (q, r) is a hit iff
+ * shared >= max(min_shared, 1) and containment(shared, |Q_q|) >= min_containment
+ * (the query is the first set of the pair, kmer-sketching.cpp:195-200; pairs
+ * sharing nothing are never hits).  Hits are written to d_hits (device, hit_cap
+ * records) in ascending (query, ref) order, each pair once; *n_hits (host)
+ * always receives the exact number of hits.  d_hits == NULL is a size query;
+ * *n_hits > hit_cap -> SKS_E_LENGTH, the contents of d_hits then unspecified.
+ * The call waits for the stream (it reads the count back); the final sort into
+ * d_hits is queued on it.  >= 2^32 elements on a side -> SKS_E_UNSUPPORTED, and
+ * so is a layout the build could not place (adversarial 128-bit values): no
+ * hit is reported from an invalid layout. */
+int sks_search(sks_ctx* ctx, const uint64_t* d_q_data, const uint64_t* d_q_starts, const uint32_t* d_q_sizes,
+               uint32_t q_n, uint32_t q_max_size, uint64_t q_total, const uint64_t* d_r_data,
+               const uint64_t* d_r_starts, const uint32_t* d_r_sizes, uint32_t r_n, uint32_t r_max_size,
+               uint64_t r_total, int elem_words, int kmer_num_ones, double min_containment, int32_t min_shared,
+               sks_hit* d_hits, uint64_t hit_cap, uint64_t* n_hits);
+/* The same for two sketch sets (queries == refs is allowed).  Both must share
+ * window, mask, elem_words, policy kind, hash flavour and nonce, and for
+ * SKS_FRAC_MOD the policy param (bottom-s sets of different s may be compared);
+ * a mismatch is SKS_E_ARG naming the field.  kmer_num_ones = popcount(mask) / 2;
+ * the group bounds are the mask-derived ones (sks_join_layout_bounds_for_mask);
+ * if a layout cannot be placed with them, the search runs once more with
+ * bounds sampled from the references before giving up. */
+int sks_search_sets(sks_ctx* ctx, const sks_sketch_set* queries, const sks_sketch_set* refs,
+                    double min_containment, int32_t min_shared, sks_hit* d_hits, uint64_t hit_cap,
+                    uint64_t* n_hits);
+/* Diagnostics: 64-sketch reference blocks per batch of sks_search (0, the
+ * default: the engine's choice, which keeps a batch's count tiles within 256 MiB). */
+int sks_ctx_set_search_batch(sks_ctx* ctx, uint32_t ref_blocks);
+
 /* Pinned host memory the device reads and writes directly (mapped into every
  * device's address space): the destination of a fused ANI matrix.  coherent:
  * fine-grained (every device store goes to the host as issued); 0: coarse-

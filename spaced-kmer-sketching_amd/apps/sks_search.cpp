@@ -1,0 +1,136 @@
+// sks-search — a sketch database and thresholded queries against it, on the
+// C ABI (include/sks.h); no reference counterpart.
+//
+//   sks-search index <out.sks> <w> <k> <c> <a.fa> <b.fa> ...
+//       one FracMinHash sketch (1/c) per FASTA file under the seed-0 spaced mask
+//       of (w, k), stored with the file names (sks_sketch_set_save)
+//   sks-search query <db.sks> <min_containment> <out.csv> <q.fa> ...
+//       sketches the queries with the database's window, mask and policy and
+//       writes every (query, reference) pair whose containment of the query is
+//       at least min_containment (sks_search_sets):
+//         Query,Reference,Shared,Containment,ANI     (doubles as %.17g)
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "sks.h"
+
+namespace {
+
+void check(int rc) {
+  if (rc != SKS_OK) throw std::runtime_error(std::string(sks_last_error()) + " (status " + std::to_string(rc) + ")");
+}
+
+void check_hip(hipError_t e, const char* what) {
+  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// One sketch per file: the files' record streams back to back in device memory,
+// a segment per file, one build; the file names become the sketch names.
+sks_sketch_set* sketch_files(sks_ctx* ctx, int n, char* files[], int window, const uint64_t mask[2],
+                             const sks_policy& policy) {
+  std::vector<uint8_t> stream;
+  std::vector<uint64_t> seg_off{0};
+  for (int i = 0; i < n; ++i) {
+    sks_fasta* f = nullptr;
+    check(sks_fasta_open(files[i], &f));
+    const uint64_t bytes = sks_fasta_stream_bytes(f);
+    if (bytes) stream.insert(stream.end(), sks_fasta_stream(f), sks_fasta_stream(f) + bytes);
+    sks_fasta_close(f);
+    seg_off.push_back(stream.size());
+  }
+  void* d_seq = nullptr;
+  check_hip(hipMalloc(&d_seq, stream.size() ? stream.size() : 1), "hipMalloc");
+  if (!stream.empty()) check_hip(hipMemcpy(d_seq, stream.data(), stream.size(), hipMemcpyHostToDevice), "hipMemcpy");
+  sks_sketch_set* set = nullptr;
+  const int rc = sks_sketch_build(ctx, static_cast<const uint8_t*>(d_seq), stream.size(), seg_off.data(),
+                                  (uint32_t)n, window, mask, &policy, &set);
+  if (rc == SKS_OK) (void)sks_ctx_synchronize(ctx);
+  (void)hipFree(d_seq);
+  check(rc);
+  std::vector<const char*> names(files, files + n);
+  check(sks_sketch_set_set_names(set, names.data()));
+  return set;
+}
+
+int usage(const char* argv0) {
+  std::fprintf(stderr,
+               "usage: %s index <out.sks> <w> <k> <c> <fasta files...>\n"
+               "       %s query <db.sks> <min_containment> <out.csv> <fasta files...>\n",
+               argv0, argv0);
+  return 64;
+}
+
+int run(int argc, char* argv[]) {
+  const std::string mode = argc > 1 ? argv[1] : "";
+  sks_ctx* ctx = nullptr;
+  if (mode == "index" && argc >= 7) {
+    const int w = std::atoi(argv[3]), k = std::atoi(argv[4]);
+    const uint64_t c = std::strtoull(argv[5], nullptr, 10);
+    uint64_t mask[2];
+    check(sks_mask_generate(w, k, 0, mask));
+    check(sks_ctx_create(0, nullptr, &ctx));
+    const sks_policy policy{SKS_FRAC_MOD, SKS_HASH_BOOST_MIX, c, 1};
+    sks_sketch_set* set = sketch_files(ctx, argc - 6, argv + 6, w, mask, policy);
+    check(sks_sketch_set_save(set, argv[2]));
+    std::printf("%u sketches -> %s\n", sks_sketch_set_num(set), argv[2]);
+    sks_sketch_set_free(set);
+    sks_ctx_destroy(ctx);
+    return 0;
+  }
+  if (mode == "query" && argc >= 6) {
+    char* end = nullptr;
+    const double min_containment = std::strtod(argv[3], &end);
+    if (end == argv[3] || *end) throw std::runtime_error(std::string("bad min_containment: ") + argv[3]);
+    check(sks_ctx_create(0, nullptr, &ctx));
+    sks_sketch_set* db = nullptr;
+    check(sks_sketch_set_load(ctx, argv[2], &db));
+    sks_sketch_info info{};
+    check(sks_sketch_set_info(db, &info));
+    sks_sketch_set* q = sketch_files(ctx, argc - 5, argv + 5, info.window, info.mask, info.policy);
+    uint64_t n = 0;
+    check(sks_search_sets(ctx, q, db, min_containment, 1, nullptr, 0, &n));
+    std::vector<sks_hit> hits(n);
+    if (n) {
+      void* d_hits = nullptr;
+      check_hip(hipMalloc(&d_hits, n * sizeof(sks_hit)), "hipMalloc");
+      const int rc = sks_search_sets(ctx, q, db, min_containment, 1, static_cast<sks_hit*>(d_hits), n, &n);
+      if (rc == SKS_OK && sks_ctx_synchronize(ctx) == SKS_OK)
+        check_hip(hipMemcpy(hits.data(), d_hits, n * sizeof(sks_hit), hipMemcpyDeviceToHost), "hipMemcpy");
+      (void)hipFree(d_hits);
+      check(rc);
+    }
+    FILE* out = std::fopen(argv[4], "w");
+    if (!out) throw std::runtime_error(std::string("cannot write ") + argv[4]);
+    std::fprintf(out, "Query,Reference,Shared,Containment,ANI\n");
+    for (const sks_hit& h : hits) {
+      const char* ref = sks_sketch_set_name(db, h.ref);
+      const std::string ref_name = ref ? ref : std::to_string(h.ref);
+      std::fprintf(out, "%s,%s,%d,%.17g,%.17g\n", argv[5 + h.query], ref_name.c_str(), h.shared, h.containment,
+                   h.ani);
+    }
+    std::fclose(out);
+    std::printf("%llu hits -> %s\n", (unsigned long long)n, argv[4]);
+    sks_sketch_set_free(q);
+    sks_sketch_set_free(db);
+    sks_ctx_destroy(ctx);
+    return 0;
+  }
+  return usage(argv[0]);
+}
+
+}  // namespace
+
+int main(int argc, char* argv[]) {
+  try {
+    return run(argc, argv);
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "sks-search: %s\n", e.what());
+    return 1;
+  }
+}

@@ -1,0 +1,26 @@
+// search.hpp — query-vs-reference search over the facade's kmer_sets (no
+// reference equivalent): sks_search of libsks.so on host sets.
+#pragma once
+
+#include <vector>
+
+#include "kmer.hpp"
+
+namespace sks {
+
+struct search_hit {
+  uint32_t query, ref;  // indices into the two vectors
+  int shared;           // kmer_set_intersection(queries[query], refs[ref])
+  double containment;   // containment(shared, queries[query].kmer_set_size())
+  double ani;           // binomial_estimator(containment, mask.count() / NUCLEOTIDE_BIT_SIZE)
+};
+
+// Every (query, ref) pair sharing at least max(min_shared, 1) k-mers whose
+// containment is >= min_containment, in ascending (query, ref) order.  Both
+// vectors are uploaded once (device-resident for the call) and compared on the
+// GPU in reference batches; only the hits come back.  Every non-empty set must
+// hold k-mers of one common mask (std::invalid_argument otherwise).
+std::vector<search_hit> search_hits(const std::vector<kmer_set>& queries, const std::vector<kmer_set>& refs,
+                                    double min_containment, int min_shared);
+
+}  // namespace sks

@@ -13,8 +13,12 @@
 
 namespace sks {
 
+__device__ __forceinline__ double containment_of(int32_t inter, int32_t size_first) {
+  return inter == 0 ? 0.0 : (double)inter / (double)size_first;
+}
+
 __device__ __forceinline__ double ani_of(int32_t inter, int32_t size_first, double inv_k, double* cont) {
-  const double c = inter == 0 ? 0.0 : (double)inter / (double)size_first;
+  const double c = containment_of(inter, size_first);
   if (cont) *cont = c;
   return c <= 0.0 ? 0.0 : pow(c, inv_k);
 }

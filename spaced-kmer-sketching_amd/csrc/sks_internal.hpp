@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+struct sks_hit;  // include/sks.h
+
 namespace sks {
 
 // Small host<->device copies through a per-thread pinned staging buffer,
@@ -249,7 +251,7 @@ uint32_t join_log_b(uint32_t max_size);    // bucket count for a largest sketch 
 // at the first launch of one of its kernels (post.hip's, with the rocPRIM sorts,
 // is 14 MB and takes ~30 ms), so sks_ctx_create launches one empty kernel per
 // unit (load_code_objects, api.cpp) and a context's first build does not pay it.
-#define SKS_TU_LIST(X) X(ani) X(ingress) X(intersect) X(join) X(layout) X(post) X(scan) X(windows)
+#define SKS_TU_LIST(X) X(ani) X(ingress) X(intersect) X(join) X(layout) X(post) X(scan) X(search) X(windows)
 #define SKS_DECLARE_HOOK(tu) hipError_t code_object_hook_##tu(hipStream_t s);
 SKS_TU_LIST(SKS_DECLARE_HOOK)
 #undef SKS_DECLARE_HOOK
@@ -313,6 +315,28 @@ hipError_t launch_ani_matrix(const int32_t* counts, uint32_t n, int kmer_num_one
 // (both orientations of each pair); sizes[i] = |S_i|.
 hipError_t launch_ani_tiles(const int32_t* packed, const uint32_t* tiles, uint64_t n_tiles, uint32_t n,
                             const int32_t* sizes, int kmer_num_ones, double* out, hipStream_t s);
+
+// ---- query-vs-reference search (search.hip) ----------------------------------------------------
+// Hits of one reference batch: `packed` holds the batch's count tiles
+// [b_blocks][q_blocks][64][64] (tile bj * q_blocks + qi: query block qi against
+// batch block bj, rows = queries).  Cell (q, r) with q < nq and r < n_batch is
+// a hit iff count >= min_shared (>= 1) and containment_of(count, q_sizes[q]) >=
+// min_containment; its record {q, ref0 + r, count, |Q_q|, containment, ANI}
+// goes to hits[slot], slot taken from *counter (one atomicAdd per wavefront),
+// and is stored only when slot < cap: *counter ends as the exact hit count.
+// stat_q / stat_b: the two layouts' status words; a non-zero word 1 (invalid
+// layout) makes the launch a no-op.  root: optional ANI table for query sets of
+// root_size elements (sks_ctx_ani_table).
+hipError_t launch_search_hits(const int32_t* packed, uint32_t q_blocks, uint32_t b_blocks, uint32_t nq,
+                              uint32_t ref0, uint32_t n_batch, const uint32_t* q_sizes, double min_containment,
+                              int32_t min_shared, int kmer_num_ones, const double* root, uint32_t root_size,
+                              const uint32_t* stat_q, const uint32_t* stat_b, sks_hit* hits, uint64_t cap,
+                              unsigned long long* counter, hipStream_t s);
+// keys[i] = hits[i].query << ref_bits | hits[i].ref, idx[i] = i; and
+// dst[i] = src[idx[i]] (the records in sorted-key order).
+hipError_t launch_search_keys(const sks_hit* hits, uint64_t n, int ref_bits, uint64_t* keys, uint64_t* idx,
+                              hipStream_t s);
+hipError_t launch_search_gather(const sks_hit* src, const uint64_t* idx, uint64_t n, sks_hit* dst, hipStream_t s);
 
 // ---- device FASTA ingress (ingress.hip) -------------------------------------------------
 // strings_from_fasta on the device: writes the host parser's record stream

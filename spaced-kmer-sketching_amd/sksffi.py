@@ -74,7 +74,13 @@ EXPORTED = [
     "sks_sketches_export", "sks_all_pairs_ani", "sks_windows_dense", "sks_windows_dense_row_words",
     "sks_join_layout_bounds_for_mask", "sks_layout_tiles_ani",
     "sks_ctx_set_frac_post", "sks_ctx_last_build_path",
+    "sks_search", "sks_search_sets", "sks_ctx_set_search_batch",
 ]
+
+# sks_hit (include/sks.h): one record of Context.search's result
+HIT_DTYPE = np.dtype([("query", "<u4"), ("ref", "<u4"), ("shared", "<i4"), ("query_size", "<i4"),
+                      ("containment", "<f8"), ("ani", "<f8")])
+assert HIT_DTYPE.itemsize == 32
 
 _lib = None
 
@@ -216,6 +222,11 @@ def lib():
     L.sks_intersect_sym_tiles.restype = C.c_uint64
     L.sks_synth_bases.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double,
                                   C.c_uint64]
+    L.sks_search.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, C.c_uint32,
+                             C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_double, C.c_int32, vp, C.c_uint64,
+                             u64p]
+    L.sks_search_sets.argtypes = [vp, vp, vp, C.c_double, C.c_int32, vp, C.c_uint64, u64p]
+    L.sks_ctx_set_search_batch.argtypes = [vp, C.c_uint32]
     _lib = L
     return L
 
@@ -631,6 +642,61 @@ class Context:
                       out_ptr):
         check(lib().sks_intersect_sym(self.h, data_ptr, starts_ptr, sizes_ptr, elem_words, n,
                                       tile_begin, tile_end, out_ptr))
+
+    def set_search_batch(self, ref_blocks):
+        """sks_ctx_set_search_batch: 64-sketch reference blocks per batch of search (0: the engine's choice)."""
+        check(lib().sks_ctx_set_search_batch(self.h, C.c_uint32(int(ref_blocks))))
+
+    def search_sets_raw(self, queries, refs, min_containment, min_shared, d_hits, hit_cap):
+        """sks_search_sets with a caller buffer (device pointer or 0 for a size
+        query); returns (status code, exact hit count) without raising on
+        SKS_E_LENGTH, so a caller can see the count a short buffer still reports."""
+        n = C.c_uint64(0)
+        rc = lib().sks_search_sets(self.h, queries.h, refs.h, float(min_containment), int(min_shared),
+                                   C.c_void_p(d_hits) if d_hits else None, int(hit_cap), C.byref(n))
+        if rc not in (SKS_OK, SKS_E_LENGTH):
+            check(rc)
+        return rc, int(n.value)
+
+    def search_arrays(self, q, r, elem_words, kmer_num_ones, min_containment=0.0, min_shared=1):
+        """sks_search, the device-array form: q and r are (data, starts, sizes, n,
+        max_size, total) with device pointers (0 allowed when n is 0).  A size
+        query, then a fill; returns a HIT_DTYPE array in (query, ref) order."""
+        import torch
+        v = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+
+        def call(d_hits, cap, n):
+            check(lib().sks_search(self.h, v(q[0]), v(q[1]), v(q[2]), int(q[3]), int(q[4]), int(q[5]),
+                                   v(r[0]), v(r[1]), v(r[2]), int(r[3]), int(r[4]), int(r[5]), elem_words,
+                                   kmer_num_ones, float(min_containment), int(min_shared), v(d_hits), cap,
+                                   C.byref(n)))
+        n = C.c_uint64(0)
+        call(0, 0, n)
+        if n.value == 0:
+            return np.zeros(0, dtype=HIT_DTYPE)
+        cap = int(n.value)
+        buf = torch.empty(cap * HIT_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        call(buf.data_ptr(), cap, n)
+        self.synchronize()
+        return buf.cpu().numpy().view(HIT_DTYPE)[:int(n.value)].copy()
+
+    def search(self, queries, refs, min_containment=0.0, min_shared=1):
+        """sks_search_sets: the (query, ref) pairs of two SketchSets sharing at least
+        max(min_shared, 1) k-mers with containment(shared, |query|) >=
+        min_containment, as a HIT_DTYPE array in (query, ref) order.  A size
+        query, then a fill of a device buffer of exactly that many records."""
+        import torch
+        n = C.c_uint64(0)
+        check(lib().sks_search_sets(self.h, queries.h, refs.h, float(min_containment), int(min_shared), None, 0,
+                                    C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=HIT_DTYPE)
+        cap = int(n.value)
+        buf = torch.empty(cap * HIT_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        check(lib().sks_search_sets(self.h, queries.h, refs.h, float(min_containment), int(min_shared),
+                                    C.c_void_p(buf.data_ptr()), cap, C.byref(n)))
+        self.synchronize()
+        return buf.cpu().numpy().view(HIT_DTYPE)[:int(n.value)].copy()
 
     def synth_bases(self, d_out_ptr, n, seed, mut_seed=0, mut_rate=0.0, pos_offset=0):
         check(lib().sks_synth_bases(self.h, C.c_void_p(d_out_ptr), n, seed, mut_seed, mut_rate,
