@@ -1,4 +1,4 @@
-"""The fused post-processing of one narrow FracMinHash genome (api.cpp
+"""The fused post-processing of one narrow FracMinHash genome (build.cpp
 build_frac_single, post.hip k_frac_partition / k_frac_sort_unique /
 k_frac_gather) against the oracle, bit-exactly: sketch, size and windows.
 
