@@ -25,7 +25,8 @@ extern "C" {
 #define SKS_ABI_VERSION 3  /* 3: a join layout's boff row ends with one more word, the log2 of
                               the buckets per region, which the join reads: layouts built by
                               an ABI-2 library (rows without that word) must not be joined by
-                              this one (round 5).  2: deduplicated join layout (masks, region
+                              this one (round 5); later additions within 3 (new symbols
+                              only): sks_sketch_set_downsample.  2: deduplicated join layout (masks, region
                               ends), elem_words on the layout entry points,
                               sks_ctx_set_join_check; later additions within 2 (new symbols
                               only): sks_ani_rows, sks_intersect_layout_ani, sks_host_alloc,
@@ -198,6 +199,22 @@ int sks_sketch_set_load(sks_ctx* ctx, const char* path, sks_sketch_set** out);
  * window, mask and policy. */
 int sks_sketch_set_concat(sks_ctx* ctx, const sks_sketch_set* const* sets, uint32_t n_sets,
                           sks_sketch_set** out);
+/* A coarser copy of `set` on the context's device, identical to what
+ * sks_sketch_build would give for the same sequences with policy.param = param:
+ *  SKS_FRAC_MOD: param must be a multiple of the set's param (else SKS_E_ARG
+ *    naming "policy param"); keeps x iff frac_min_hash(x) % param == 0.
+ *  SKS_BOTTOM_S: 0 < param <= the set's param (else SKS_E_ARG); every sketch keeps
+ *    its min(param, size) elements smallest by (frac_min_hash, k-mer value).
+ * Elements stay ascending and unique; window, mask, flavour, nonce, elem_words,
+ * per-sketch windows and names are carried over; info.policy.param = param.
+ * param equal to the set's gives a copy.  The source set is not modified.
+ * A null ctx, set or out, param == 0 and a set on another device than the
+ * context's are SKS_E_ARG; *out is NULL on every failure.
+ * Waits for the context's stream once (it reads the new sizes back); the
+ * elements are then written by a kernel queued on that stream, like the output
+ * of every queued call (sks_ctx_synchronize waits for it; the source set may be
+ * freed with sks_sketch_set_free at once). */
+int sks_sketch_set_downsample(sks_ctx* ctx, const sks_sketch_set* set, uint64_t param, sks_sketch_set** out);
 
 /* ---- ordered k-mer lists: nucleotide_string_list_to_kmers (kmer_sliding.cpp:112-238) ---
  * Every selected window of every segment, in stream order, duplicates kept —

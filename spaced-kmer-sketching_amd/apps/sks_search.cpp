@@ -9,6 +9,10 @@
 //       writes every (query, reference) pair whose containment of the query is
 //       at least min_containment (sks_search_sets):
 //         Query,Reference,Shared,Containment,ANI     (doubles as %.17g)
+//   sks-search downsample <in.sks> <c> <out.sks>
+//       a coarser copy of a database (sks_sketch_set_downsample): FracMinHash 1/c
+//       with c a multiple of the database's, or bottom-s with a smaller s; the
+//       result equals a database indexed at c directly, names kept
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -61,8 +65,9 @@ sks_sketch_set* sketch_files(sks_ctx* ctx, int n, char* files[], int window, con
 int usage(const char* argv0) {
   std::fprintf(stderr,
                "usage: %s index <out.sks> <w> <k> <c> <fasta files...>\n"
-               "       %s query <db.sks> <min_containment> <out.csv> <fasta files...>\n",
-               argv0, argv0);
+               "       %s query <db.sks> <min_containment> <out.csv> <fasta files...>\n"
+               "       %s downsample <in.sks> <c> <out.sks>\n",
+               argv0, argv0, argv0);
   return 64;
 }
 
@@ -117,6 +122,23 @@ int run(int argc, char* argv[]) {
     std::fclose(out);
     std::printf("%llu hits -> %s\n", (unsigned long long)n, argv[4]);
     sks_sketch_set_free(q);
+    sks_sketch_set_free(db);
+    sks_ctx_destroy(ctx);
+    return 0;
+  }
+  if (mode == "downsample" && argc == 5) {
+    char* end = nullptr;
+    const uint64_t c = std::strtoull(argv[3], &end, 10);
+    if (end == argv[3] || *end) throw std::runtime_error(std::string("bad c: ") + argv[3]);
+    check(sks_ctx_create(0, nullptr, &ctx));
+    sks_sketch_set* db = nullptr;
+    check(sks_sketch_set_load(ctx, argv[2], &db));
+    sks_sketch_set* small = nullptr;
+    check(sks_sketch_set_downsample(ctx, db, c, &small));
+    check(sks_ctx_synchronize(ctx));
+    check(sks_sketch_set_save(small, argv[4]));
+    std::printf("%u sketches -> %s\n", sks_sketch_set_num(small), argv[4]);
+    sks_sketch_set_free(small);
     sks_sketch_set_free(db);
     sks_ctx_destroy(ctx);
     return 0;

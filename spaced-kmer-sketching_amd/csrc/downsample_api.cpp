@@ -1,0 +1,142 @@
+// C-ABI implementation (include/sks.h): sks_sketch_set_downsample — a coarser
+// copy of a device sketch set (FracMinHash 1/c -> 1/c', bottom-s -> bottom-s')
+// made from the set's own elements by the filter kernels of downsample.hip.
+#include <numeric>
+
+#include "sks_ctx.hpp"
+#include "sks_hash.hpp"
+
+using namespace sks;
+
+namespace {
+
+// The new set while it is being filled: freed on every early return.
+struct SetHolder {
+  sks_sketch_set* set = nullptr;
+  ~SetHolder() {
+    if (set) sks_sketch_set_free(set);
+  }
+};
+
+}  // namespace
+
+extern "C" int sks_sketch_set_downsample(sks_ctx* c, const sks_sketch_set* src, uint64_t param,
+                                         sks_sketch_set** out) {
+  if (out) *out = nullptr;
+  if (!c || !src || !out) return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: null argument");
+  if (param == 0) return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: policy param must be > 0");
+  if (src->device != c->device)
+    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: the set is on device " + std::to_string(src->device) +
+                                    ", the context on device " + std::to_string(c->device));
+  const sks_policy& pol = src->policy;
+  const bool bottom = pol.kind == SKS_BOTTOM_S;
+  if (!bottom && pol.kind != SKS_FRAC_MOD)
+    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: unknown policy kind");
+  if (pol.flavour != 0 && pol.flavour != 1)
+    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: unknown hash flavour");
+  if (src->elem_words != 1 && src->elem_words != 2)
+    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: elements of 1 or 2 words only");
+  if (!bottom && (pol.param == 0 || param % pol.param != 0))
+    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: policy param " + std::to_string(param) +
+                                    " is not a multiple of the set's " + std::to_string(pol.param) +
+                                    " (a FracMinHash sketch can only be made coarser)");
+  if (bottom && param > pol.param)
+    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: policy param " + std::to_string(param) +
+                                    " is larger than the set's " + std::to_string(pol.param) +
+                                    " (a bottom-s sketch can only be made smaller)");
+
+  DeviceGuard guard(c->device);
+  hipStream_t st = c->stream;
+  const uint32_t n = src->n;
+  const int ew = src->elem_words;
+
+  // chunks and elements before each sketch
+  std::vector<uint64_t> chunk_off(n + 1, 0), dense_off(n + 1, 0);
+  uint64_t max_len = 0;
+  bool selects = false;  // bottom-s: a sketch holds more than `param` elements
+  for (uint32_t g = 0; g < n; ++g) {
+    const uint64_t sz = src->sizes[g];
+    chunk_off[g + 1] = chunk_off[g] + (sz + kDownsampleChunk - 1) / kDownsampleChunk;
+    dense_off[g + 1] = dense_off[g] + sz;
+    max_len = std::max(max_len, sz);
+    selects = selects || sz > param;
+  }
+  const uint64_t n_chunks = chunk_off[n], T = dense_off[n];
+  const int mode = !bottom ? (param == pol.param ? kDownsampleAll : kDownsampleFrac)
+                           : (selects ? kDownsampleFlag : kDownsampleAll);
+
+  SetHolder hold;
+  hold.set = new (std::nothrow) sks_sketch_set();
+  if (!hold.set) return sks::fail(SKS_E_NOMEM, "sks_sketch_set_downsample: out of memory");
+  sks_sketch_set* set = hold.set;
+  set->device = c->device;
+  set->elem_words = ew;
+  set->n = n;
+  set->windows = src->windows;
+  set->window = src->window;
+  set->mask[0] = src->mask[0];
+  set->mask[1] = src->mask[1];
+  set->policy = pol;
+  set->policy.param = param;
+  set->names = src->names;
+  set->sizes.assign(n, 0);  // what release_set_arrays sizes d_data by, should a step below fail
+  set->starts.assign(n, 0);
+  SKS_TRY(alloc_u64(&set->d_starts, n));
+  SKS_HIP(dev_alloc(reinterpret_cast<void**>(&set->d_sizes), std::max<uint32_t>(n, 1) * sizeof(uint32_t)));
+
+  MetaArena arena(c);
+  const size_t o_chunk = arena.add(chunk_off), o_dense = arena.add(dense_off);
+  SKS_TRY(arena.upload());
+  SKS_HIP(c->flag.reserve((n_chunks + 1) * sizeof(uint32_t)));
+  SKS_HIP(c->pos.reserve((n_chunks + 1) * sizeof(uint64_t)));
+  uint32_t* d_counts = reinterpret_cast<uint32_t*>(c->flag.ptr);
+  uint64_t* d_offs = reinterpret_cast<uint64_t*>(c->pos.ptr);
+
+  DownsampleArgs a{};
+  a.data = src->d_data;
+  a.starts = src->d_starts;
+  a.sizes = src->d_sizes;
+  a.chunk_off = arena.ptr(o_chunk);
+  a.dense_off = arena.ptr(o_dense);
+  a.kconst = sks::fmh_const(src->mask[0], src->mask[1], src->window, pol.nonce, pol.flavour);
+  if (mode == kDownsampleFrac) {
+    const sks::DivTest dt = sks::make_div_test(param);
+    a.low_mask = dt.low_mask;
+    a.high_mask = dt.rot > 32 ? (uint32_t)((1ull << (dt.rot - 32)) - 1) : 0u;
+    a.dinv = dt.dinv;
+    a.dlim = dt.lim;
+  }
+  if (mode == kDownsampleFlag) {
+    // (fmh, index) sorted by fmh within each sketch: the sort is stable and the
+    // elements ascend by k-mer, so a sketch's first `param` entries are its
+    // smallest by (fmh, k-mer), ties at the last fmh taken in k-mer order
+    SKS_TRY(reserve_cols(c, {0, 1, 2, 3, 4}, T + 1));
+    uint32_t* d_keep = reinterpret_cast<uint32_t*>(col(c, 2));
+    SKS_HIP(sks::downsample_fmh(a, ew, pol.flavour, n, max_len, col(c, 0), col(c, 1), st));
+    SKS_HIP(sks::seg_sort_pairs(col(c, 0), col(c, 3), col(c, 1), col(c, 4), T, dense_off, a.dense_off, 64, c->tmp,
+                                st));
+    SKS_HIP(hipMemsetAsync(d_keep, 0, T * sizeof(uint32_t), st));
+    SKS_HIP(sks::downsample_mark(a, n, param, max_len, col(c, 4), d_keep, st));
+    a.keep_flag = d_keep;
+  }
+
+  SKS_HIP(sks::downsample_count(a, ew, pol.flavour, mode, n, max_len, d_counts, st));
+  SKS_HIP(sks::downsample_offsets(d_counts, n_chunks, d_offs, a.chunk_off, n, set->d_starts, set->d_sizes, c->tmp,
+                                  st));
+  // the call's one wait: the new sizes size the new set's data array exactly
+  std::vector<uint32_t> sizes(n, 0);
+  SKS_HIP(sks::pinned_d2h(sizes.data(), set->d_sizes, n * sizeof(uint32_t), st));
+  uint64_t total = 0;
+  for (uint32_t g = 0; g < n; ++g) {
+    if (sizes[g] > src->sizes[g])
+      return sks::fail(SKS_E_HIP, "sks_sketch_set_downsample: a filtered sketch is larger than its source");
+    set->starts[g] = total;
+    total += sizes[g];
+  }
+  SKS_TRY(alloc_u64(&set->d_data, total * ew));
+  set->sizes = sizes;
+  SKS_HIP(sks::downsample_scatter(a, ew, pol.flavour, mode, n, max_len, d_offs, set->d_data, st));
+  *out = hold.set;
+  hold.set = nullptr;
+  return SKS_OK;
+}

@@ -1,5 +1,5 @@
 // What the C-ABI translation units that run on a device share (ctx.cpp,
-// host_mem.cpp, build.cpp, pairs.cpp, search_api.cpp): the context, the error
+// host_mem.cpp, build.cpp, pairs.cpp, search_api.cpp, downsample_api.cpp): the context, the error
 // macros, the metadata arena, the device block cache and small argument helpers.
 #pragma once
 #include <hip/hip_runtime.h>

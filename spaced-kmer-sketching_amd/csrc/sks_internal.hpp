@@ -251,7 +251,7 @@ uint32_t join_log_b(uint32_t max_size);    // bucket count for a largest sketch 
 // at the first launch of one of its kernels (post.hip's, with the rocPRIM sorts,
 // is 14 MB and takes ~30 ms), so sks_ctx_create launches one empty kernel per
 // unit (load_code_objects, api.cpp) and a context's first build does not pay it.
-#define SKS_TU_LIST(X) X(ani) X(ingress) X(intersect) X(join) X(layout) X(post) X(scan) X(search) X(windows)
+#define SKS_TU_LIST(X) X(ani) X(downsample) X(ingress) X(intersect) X(join) X(layout) X(post) X(scan) X(search) X(windows)
 #define SKS_DECLARE_HOOK(tu) hipError_t code_object_hook_##tu(hipStream_t s);
 SKS_TU_LIST(SKS_DECLARE_HOOK)
 #undef SKS_DECLARE_HOOK
@@ -337,6 +337,43 @@ hipError_t launch_search_hits(const int32_t* packed, uint32_t q_blocks, uint32_t
 hipError_t launch_search_keys(const sks_hit* hits, uint64_t n, int ref_bits, uint64_t* keys, uint64_t* idx,
                               hipStream_t s);
 hipError_t launch_search_gather(const sks_hit* src, const uint64_t* idx, uint64_t n, sks_hit* dst, hipStream_t s);
+
+// ---- sketch-set downsampling (downsample.hip) ----------------------------------------------
+// An order-preserving filter over a set's CSR arrays: workgroups own chunks of
+// kDownsampleChunk consecutive elements of one sketch on a (chunk, sketch) grid;
+// chunk_off[g] = chunks before sketch g (chunk_off[n] = all chunks).
+constexpr uint32_t kDownsampleChunk = 1024;
+constexpr int kDownsampleFrac = 0;  // keep x iff frac_min_hash(x) % c == 0 (the DivTest words below)
+constexpr int kDownsampleFlag = 1;  // keep the set's d-th element iff keep_flag[d] != 0
+constexpr int kDownsampleAll = 2;   // a copy
+struct DownsampleArgs {
+  const uint64_t* data;        // the source set's arrays
+  const uint64_t* starts;
+  const uint32_t* sizes;
+  const uint64_t* chunk_off;   // [n + 1]
+  const uint64_t* dense_off;   // [n + 1] elements before each sketch (flag mode and the bottom-s helpers)
+  const uint32_t* keep_flag;   // flag mode
+  uint64_t kconst;             // fmh_const of the set
+  uint32_t low_mask, high_mask;
+  uint64_t dinv, dlim;
+  uint32_t g0;                 // set by the launchers: first sketch of a grid slice
+};
+// counts[chunk] = kept elements of every chunk (n sketches, the longest of max_len elements)
+hipError_t downsample_count(const DownsampleArgs& args, int ew, int flavour, int mode, uint32_t n, uint64_t max_len,
+                            uint32_t* counts, hipStream_t s);
+// offs[0 .. n_chunks] = exclusive scan of counts (counts needs n_chunks + 1 words), and from it
+// starts[g], sizes[g] of the filtered set
+hipError_t downsample_offsets(uint32_t* counts, uint64_t n_chunks, uint64_t* offs, const uint64_t* chunk_off,
+                              uint32_t n, uint64_t* starts, uint32_t* sizes, Scratch& tmp, hipStream_t s);
+// out[offs[chunk] + rank] = the chunk's kept elements, in order
+hipError_t downsample_scatter(const DownsampleArgs& args, int ew, int flavour, int mode, uint32_t n,
+                              uint64_t max_len, const uint64_t* offs, uint64_t* out, hipStream_t s);
+// bottom-s: fmh[d] = frac_min_hash of the d-th element, idx[d] = d; and, from idx sorted by fmh
+// within each sketch (stable), keep_flag[d] = 1 for each sketch's first min(limit, size) (keep_flag zeroed)
+hipError_t downsample_fmh(const DownsampleArgs& args, int ew, int flavour, uint32_t n, uint64_t max_len,
+                          uint64_t* fmh, uint64_t* idx, hipStream_t s);
+hipError_t downsample_mark(const DownsampleArgs& args, uint32_t n, uint64_t limit, uint64_t max_len,
+                           const uint64_t* idx_sorted, uint32_t* keep_flag, hipStream_t s);
 
 // ---- device FASTA ingress (ingress.hip) -------------------------------------------------
 // strings_from_fasta on the device: writes the host parser's record stream

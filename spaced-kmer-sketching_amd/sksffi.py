@@ -74,7 +74,7 @@ EXPORTED = [
     "sks_sketches_export", "sks_all_pairs_ani", "sks_windows_dense", "sks_windows_dense_row_words",
     "sks_join_layout_bounds_for_mask", "sks_layout_tiles_ani",
     "sks_ctx_set_frac_post", "sks_ctx_last_build_path",
-    "sks_search", "sks_search_sets", "sks_ctx_set_search_batch",
+    "sks_search", "sks_search_sets", "sks_ctx_set_search_batch", "sks_sketch_set_downsample",
 ]
 
 # sks_hit (include/sks.h): one record of Context.search's result
@@ -182,6 +182,7 @@ def lib():
     L.sks_sketch_set_save.argtypes = [vp, C.c_char_p]
     L.sks_sketch_set_load.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
     L.sks_sketch_set_concat.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
+    L.sks_sketch_set_downsample.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp)]
     L.sks_kmer_list_build.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, u64p,
                                       C.POINTER(Policy), C.POINTER(vp)]
     L.sks_windows_dense.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, u64p, vp, vp]
@@ -626,6 +627,13 @@ class Context:
         arr = (C.c_void_p * len(sets))(*[s.h for s in sets])
         h = C.c_void_p()
         check(lib().sks_sketch_set_concat(self.h, arr, len(sets), C.byref(h)))
+        return SketchSet(h)
+
+    def downsample(self, sketch_set, param):
+        """sks_sketch_set_downsample: a coarser copy of a SketchSet, equal to a direct
+        build at `param` (FracMinHash: a multiple of the set's c; bottom-s: s' <= s)."""
+        h = C.c_void_p()
+        check(lib().sks_sketch_set_downsample(self.h, sketch_set.h, int(param), C.byref(h)))
         return SketchSet(h)
 
     def intersect_pairs(self, data_ptr, starts_ptr, sizes_ptr, elem_words, a_ptr, b_ptr,
