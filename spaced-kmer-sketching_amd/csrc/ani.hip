@@ -13,8 +13,9 @@
 
 #include <cstdint>
 
+#include "ani.hpp"
+#include "code_objects.hpp"
 #include "sks_ani.hpp"
-#include "sks_internal.hpp"
 
 namespace sks {
 

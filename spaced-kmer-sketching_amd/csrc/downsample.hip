@@ -21,8 +21,9 @@
 #include <rocprim/rocprim.hpp>
 #include <type_traits>
 
+#include "code_objects.hpp"
+#include "downsample.hpp"
 #include "sks_hash.hpp"
-#include "sks_internal.hpp"
 
 namespace sks {
 

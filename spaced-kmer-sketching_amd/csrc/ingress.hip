@@ -32,7 +32,10 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
-#include "sks_internal.hpp"
+#include "code_objects.hpp"
+#include "device_mem.hpp"
+#include "ingress.hpp"
+#include "wave_prims.hpp"
 
 namespace sks {
 
@@ -89,29 +92,6 @@ __device__ __forceinline__ SpanThread span_load(const uint8_t* raw, uint64_t n, 
   return t;
 }
 
-// Exclusive prefix sum over the work-group (s_tmp: one word per wave).
-__device__ __forceinline__ uint32_t block_exclusive_sum(uint32_t v, uint32_t* s_tmp,
-                                                        uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) s_tmp[wave] = x;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kB / 64; ++w) {
-    const uint32_t t = s_tmp[w];
-    base += w < wave ? t : 0u;
-    tot += t;
-  }
-  *total = tot;
-  return base + x - v;
-}
-
 __device__ __forceinline__ uint64_t line_start(const uint64_t* nl, uint64_t l) {
   return l ? nl[l - 1] + 1 : 0;
 }
@@ -126,7 +106,7 @@ __global__ __launch_bounds__(kB) void k_span_count(const uint8_t* raw, uint64_t 
   __shared__ uint32_t s_tmp[kB / 64];
   const SpanThread t = span_load(raw, n, align);
   uint32_t total;
-  (void)block_exclusive_sum(__popc(byte_eq_mask(t.q, 0x0A0A0A0Au) & t.valid), s_tmp, &total);
+  (void)block_excl_scan<kB / 64>(__popc(byte_eq_mask(t.q, 0x0A0A0A0Au) & t.valid), s_tmp, &total);
   if (threadIdx.x == 0) span_nl[blockIdx.x] = total;
 }
 
@@ -150,7 +130,7 @@ __global__ __launch_bounds__(kB) void k_span_lines(const uint8_t* raw, uint64_t 
   uint32_t nlm = byte_eq_mask(t.q, 0x0A0A0A0Au) & t.valid;
   uint32_t spm = byte_eq_mask(t.q, 0x20202020u) & t.valid;
   uint32_t total;
-  const uint64_t base = span_off[blockIdx.x] + block_exclusive_sum(__popc(nlm), s_tmp, &total);
+  const uint64_t base = span_off[blockIdx.x] + block_excl_scan<kB / 64>(__popc(nlm), s_tmp, &total);
   const uint64_t i0 = t.v0 - align;  // input index of byte 0 (when valid)
   if (blockIdx.x == 0 && threadIdx.x == 0) fb[0] = raw[0];
   while (spm) {
@@ -283,7 +263,7 @@ __global__ __launch_bounds__(kB) void k_copy(const uint8_t* raw, uint64_t n, uin
   const uint64_t ibeg = vbeg > align ? vbeg - align : 0;
   const uint32_t nlm = byte_eq_mask(t.q, 0x0A0A0A0Au) & t.valid;
   uint32_t total;
-  uint32_t j = block_exclusive_sum(__popc(nlm), s_tmp, &total);
+  uint32_t j = block_excl_scan<kB / 64>(__popc(nlm), s_tmp, &total);
   uint8_t* so = reinterpret_cast<uint8_t*>(s_out);
   for (uint32_t q = threadIdx.x; q <= total; q += kB) {
     const uint64_t l = l0 + q;

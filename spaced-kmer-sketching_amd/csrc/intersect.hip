@@ -25,8 +25,10 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "code_objects.hpp"
+#include "intersect.hpp"
+#include "join.hpp"
 #include "join_common.hpp"
-#include "sks_internal.hpp"
 
 namespace sks {
 

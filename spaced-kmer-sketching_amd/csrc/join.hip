@@ -24,14 +24,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
 #include <cstdlib>
 #include <cstdint>
-#include <vector>
 
+#include "code_objects.hpp"
+#include "join.hpp"
 #include "join_common.hpp"
 #include "sks_ani.hpp"
-#include "sks_internal.hpp"
+#include "wave_prims.hpp"
 
 namespace sks {
 
@@ -54,43 +54,28 @@ constexpr uint64_t kMaxGrid = 1ull << 22;
 // three for 128-bit values, hide the LDS round trips of the insert and probe chains
 constexpr int kJB = 512;
 constexpr int kJCap = 1024;             // column entries per chunk (10-bit entry index)
-#ifndef SKS_JOIN_CAP2
-#define SKS_JOIN_CAP2 1024
-#endif
 // column entries per chunk by value width (128-bit values: a smaller chunk
 // can buy LDS for another workgroup per CU), and per thread
 template <int EW>
-constexpr int jcap() { return EW == 1 ? kJCap : SKS_JOIN_CAP2; }
+constexpr int jcap() { return EW == 1 ? kJCap : 1024; }
 template <int EW>
 constexpr int jmade() { return jcap<EW>() / kJB; }
-static_assert(SKS_JOIN_CAP2 % kJB == 0 && SKS_JOIN_CAP2 <= kJCap, "128-bit chunk capacity");
-#ifndef SKS_JOIN_ROWPF
-#define SKS_JOIN_ROWPF 1
-#endif
-constexpr int kJRowPf = SKS_JOIN_ROWPF;   // row entries per thread held in registers per chunk
+static_assert(jcap<2>() % kJB == 0 && jcap<2>() <= kJCap, "128-bit chunk capacity");
+constexpr int kJRowPf = 1;   // row entries per thread held in registers per chunk
 // buckets per window: a workgroup stages the bucket offsets of 64 buckets at a
 // time; a window may hold several layout regions (each region's entries are
 // contiguous, with a gap before the next region: chunks map their entries
 // piecewise, at most kJPieces regions per chunk)
-#ifndef SKS_JOIN_WINLOG
-#define SKS_JOIN_WINLOG 6
-#endif
-constexpr int kJWinLog = SKS_JOIN_WINLOG, kJWin = 1 << kJWinLog;
+constexpr int kJWinLog = 6, kJWin = 1 << kJWinLog;
 static_assert(kJWinLog <= 6, "a window's buckets are scanned by one wave");
 constexpr uint32_t kJPieces = 4;
 // 12 planes hold counts below 2^12 per workgroup; a carry out of the top plane
 // (a pair sharing >= 4096 values in one workgroup's buckets) is added to the
 // output directly (16 planes cost the LDS of the fourth workgroup per CU)
-#ifndef SKS_JOIN_PLANES
-#define SKS_JOIN_PLANES 12
-#endif
-constexpr int kPlanes = SKS_JOIN_PLANES;
+constexpr int kPlanes = 12;
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 // hit items with more rows than this are spread over the wave's lanes (rows_add)
-#ifndef SKS_JOIN_LIGHT
-#define SKS_JOIN_LIGHT 2
-#endif
-constexpr uint32_t kLight = SKS_JOIN_LIGHT;
+constexpr uint32_t kLight = 2;
 static_assert(kJCap == 1024, "entry index: 10 bits of the slot word");
 static_assert(kFSlots >= kTile * kTile, "the fused ANI stages a tile's counts in the slot table");
 
@@ -193,23 +178,6 @@ __device__ __forceinline__ void join_fetch(const uint64_t* __restrict__ cvals,
 
 __device__ unsigned long long g_join_check;  // SKS check build: table invariant violations
 
-// inclusive prefix sum over the 64 lanes of a wave (DPP; no LDS)
-__device__ __forceinline__ uint32_t wave_scan(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long readlane64(unsigned long long x, uint32_t l) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, (int)l);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), (int)l);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
 // index of the k-th set bit (k < popcount(x)) of x
 __device__ __forceinline__ uint32_t nth_bit(unsigned long long x, uint32_t k) {
   uint32_t r = 0;
@@ -231,29 +199,6 @@ __device__ __forceinline__ uint32_t window_end(const uint32_t* off, uint32_t we,
   return (we & ((1u << rb_log) - 1)) == 0 ? off[B + ((we - 1) >> rb_log)] : off[we];
 }
 
-#ifdef SKS_JOIN_STAMPS  // diagnostic build: cycles per k_join phase, summed by thread 0 of each workgroup
-// slots: 0 setup, 1 window bookkeeping, 2 stage (incl. waiting for the chunk's
-// loads), 3 insert, 4 probe + hit adds, 5 flush, 6 fused ANI, 7 diagonal tile
-constexpr int kMaxJoinStampWgs = 65536;
-__device__ unsigned long long g_join_stamps_wg[kMaxJoinStampWgs * 8];
-#define JSTAMP(i)                                    \
-  do {                                               \
-    if (threadIdx.x == 0) {                          \
-      const uint64_t t_ = __builtin_amdgcn_s_memtime(); \
-      js_acc[i] += t_ - js_last;                     \
-      js_last = t_;                                  \
-    }                                                \
-  } while (0)
-#define JSTAMP_FLUSH()                                                                          \
-  do {                                                                                          \
-    if (threadIdx.x == 0 && blockIdx.x < kMaxJoinStampWgs)                                      \
-      for (int q_ = 0; q_ < 8; ++q_) g_join_stamps_wg[(uint64_t)blockIdx.x * 8 + q_] = js_acc[q_]; \
-  } while (0)
-#else
-#define JSTAMP(i) do {} while (0)
-#define JSTAMP_FLUSH() do {} while (0)
-#endif
-
 // PIECES = false: windows also end at every region end of either layout, so a
 // chunk is always contiguous (the kernel for layouts of 64-bucket regions,
 // where the piece code, never taken, still cost 8% of the join); true: windows
@@ -263,13 +208,7 @@ __device__ unsigned long long g_join_stamps_wg[kMaxJoinStampWgs * 8];
 // chunk loop), 8% faster than three with 80; 128-bit values: three (76 VGPRs,
 // 47.4 KB; four per CU with 512-entry chunks measured equal)
 template <int EW, bool CHECK, bool PIECES>
-#ifndef SKS_JOIN_WPE1
-#define SKS_JOIN_WPE1 8
-#endif
-#ifndef SKS_JOIN_WPE2
-#define SKS_JOIN_WPE2 2
-#endif
-__global__ __launch_bounds__(kJB, EW == 1 ? SKS_JOIN_WPE1 : SKS_JOIN_WPE2) void k_join(JoinArgs a) {
+__global__ __launch_bounds__(kJB, EW == 1 ? 8 : 2) void k_join(JoinArgs a) {
   __shared__ uint32_t s_slot[kFSlots];
   __shared__ uint64_t s_ev[jcap<EW>() * EW];          // staged column entries: values
   __shared__ unsigned long long s_em[jcap<EW>()];     // ... and column masks
@@ -279,10 +218,6 @@ __global__ __launch_bounds__(kJB, EW == 1 ? SKS_JOIN_WPE1 : SKS_JOIN_WPE2) void 
   __shared__ uint8_t s_next[kJWin];
   __shared__ uint32_t s_self[kTile];
   __shared__ uint32_t s_top;  // planes used (the highest carry chain)
-#ifdef SKS_JOIN_STAMPS
-  uint64_t js_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint64_t js_last = __builtin_amdgcn_s_memtime();
-#endif
 
   // tile of this workgroup: dispatch slot u, in tile order, or (diag_last) the
   // off-diagonal tiles in tile order and then the diagonal ones.  A tile's ANI
@@ -346,7 +281,6 @@ __global__ __launch_bounds__(kJB, EW == 1 ? SKS_JOIN_WPE1 : SKS_JOIN_WPE2) void 
   if (tid == 0) s_top = 0;
   uint32_t top = 0;
   __syncthreads();  // table, planes and self counts cleared before any chain (the diagonal path has no other barrier)
-  JSTAMP(0);
 
   // output of count `cnt` for tile cell (r, c) (both halves of a symmetric
   // off-diagonal tile): the carry-out path of add_hits
@@ -459,7 +393,6 @@ __global__ __launch_bounds__(kJB, EW == 1 ? SKS_JOIN_WPE1 : SKS_JOIN_WPE2) void 
       }
       wb = we;
     }
-    JSTAMP(7);
   } else {
     // ---- off-diagonal tile: chunks of the column block's entries -----------------------------
     uint32_t made[jmade<EW>()];  // slots this thread created in the current chunk
@@ -537,7 +470,6 @@ __global__ __launch_bounds__(kJB, EW == 1 ? SKS_JOIN_WPE1 : SKS_JOIN_WPE2) void 
       // chunks of whole buckets; a bucket above cap is cut into sub-chunks of
       // cap column entries, each joined with all of the bucket's row entries
       // (its column entries are distinct, so each hit is counted once)
-      JSTAMP(1);
       auto chunk_end = [&](uint32_t bs) { return wb + (uint32_t)s_next[bs - wb]; };
       uint32_t bs = wb, be = chunk_end(wb);
       uint32_t cs = s_cv[0], ce = min(s_cv[be - wb], cs + a.cap);
@@ -565,7 +497,6 @@ __global__ __launch_bounds__(kJB, EW == 1 ? SKS_JOIN_WPE1 : SKS_JOIN_WPE2) void 
           rp = pieces(s_roff, s_rv, nbs - wb, nbe - wb, r_rb, r_one);
           join_fetch<EW, PIECES>(cvals, cmasks, rvals, rmasks, ncs, nce, cp, s_rv[nbs - wb], s_rv[nbe - wb], rp, tid, nxt);
         }
-        JSTAMP(1);
 
         // 0) free the previous chunk's slots (its probes are done: barrier below
         //    the probe loop) and stage this chunk's entries
@@ -581,7 +512,6 @@ __global__ __launch_bounds__(kJB, EW == 1 ? SKS_JOIN_WPE1 : SKS_JOIN_WPE2) void 
           }
         }
         __syncthreads();
-        JSTAMP(2);
         // 1) insert: the chunk's values are distinct, so a compare-swap walk to
         //    the first free slot
 #pragma unroll
@@ -598,7 +528,6 @@ __global__ __launch_bounds__(kJB, EW == 1 ? SKS_JOIN_WPE1 : SKS_JOIN_WPE2) void 
           made[u] = h;
         }
         __syncthreads();
-        JSTAMP(3);
         if (CHECK) {  // every inserted value is found, naming its own entry
 #pragma unroll
           for (int u = 0; u < jmade<EW>(); ++u) {
@@ -646,7 +575,6 @@ __global__ __launch_bounds__(kJB, EW == 1 ? SKS_JOIN_WPE1 : SKS_JOIN_WPE2) void 
           rows_add(m ? rows : 0ull, m, false);
         }
         __syncthreads();
-        JSTAMP(4);
         cur = nxt;
         bs = nbs;
         be = nbe;
@@ -693,11 +621,7 @@ __global__ __launch_bounds__(kJB, EW == 1 ? SKS_JOIN_WPE1 : SKS_JOIN_WPE2) void 
       atomicAdd(&a.out[(uint64_t)gc * a.ld + gr], (int32_t)cnt);
     }
   }
-  JSTAMP(5);
-  if (!a.ani) {
-    JSTAMP_FLUSH();
-    return;
-  }
+  if (!a.ani) return;
   // ---- fused containment / ANI: the tile's last workgroup converts it --------------------------
   // The counts are only ever written by device-scope atomics, which every
   // workgroup's result reaches at the device's coherence point (that is what
@@ -711,22 +635,13 @@ __global__ __launch_bounds__(kJB, EW == 1 ? SKS_JOIN_WPE1 : SKS_JOIN_WPE2) void 
   // with lanes over columns and (c, r) with lanes over rows, so every wave's
   // stores are one contiguous 512-byte row segment of the n x n matrix (ani may
   // be pinned host memory: PCIe writes).
-#if SKS_ANI_DIAG != 2  // (diagnostics 2: no drain; the counts the finisher reads may be short)
   __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
-#endif
   __syncthreads();
   if (tid == 0)
     s_top = __hip_atomic_fetch_add(a.tile_done + (t - a.tile_begin), 1u, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT) + 1 == a.n_groups;
   __syncthreads();
-#if SKS_ANI_DIAG == 1  // (diagnostics 1: the hand-off only, no conversion)
-  if (s_top) return;
-#endif
-  if (!s_top) {
-    JSTAMP(6);
-    JSTAMP_FLUSH();
-    return;
-  }
+  if (!s_top) return;
   int32_t* s_cnt = reinterpret_cast<int32_t*>(s_slot);  // the table is free: 4096 counts
   for (uint32_t q = tid; q < (uint32_t)(kTile * kTile); q += kJB) {
     const uint32_t r = q / kTile, c = q % kTile, gr = row0 + r, gc = col0 + c;
@@ -755,8 +670,6 @@ __global__ __launch_bounds__(kJB, EW == 1 ? SKS_JOIN_WPE1 : SKS_JOIN_WPE2) void 
       if (gr < row_lim && gc < a.n) a.ani[(uint64_t)gc * a.n + gr] = conv(s_cnt[lane * kTile + c], a.sizes[gc]);
     }
   }
-  JSTAMP(6);
-  JSTAMP_FLUSH();
 }
 
 template <int EW, bool CHECK, bool PIECES>
@@ -777,20 +690,6 @@ hipError_t launch_join_slices(JoinArgs ja, uint64_t tile_begin, uint64_t tile_en
     hipLaunchKernelGGL((k_join<EW, CHECK, PIECES>), dim3((unsigned)(nt * ja.n_groups)), dim3(kJB), 0, s, ja);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-#ifdef SKS_JOIN_STAMPS
-    {
-      (void)hipStreamSynchronize(s);
-      const uint64_t nw = std::min<uint64_t>(nt * ja.n_groups, kMaxJoinStampWgs);
-      std::vector<unsigned long long> h(nw * 8);
-      (void)hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_join_stamps_wg), h.size() * 8);
-      double sum[8] = {0};
-      for (uint64_t b = 0; b < nw; ++b)
-        for (int q = 0; q < 8; ++q) sum[q] += (double)h[b * 8 + q];
-      fprintf(stderr, "[k_join stamps] %llu workgroups, cycles per workgroup: setup %.0f window %.0f stage %.0f "
-              "insert %.0f probe+hits %.0f flush %.0f ani %.0f diagonal %.0f\n", (unsigned long long)nw,
-              sum[0] / nw, sum[1] / nw, sum[2] / nw, sum[3] / nw, sum[4] / nw, sum[5] / nw, sum[6] / nw, sum[7] / nw);
-    }
-#endif
   }
   return hipSuccess;
 }

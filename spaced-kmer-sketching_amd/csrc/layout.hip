@@ -35,12 +35,12 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdio>
 #include <cstdlib>
-#include <vector>
 
+#include "code_objects.hpp"
+#include "join.hpp"
 #include "join_common.hpp"
-#include "sks_internal.hpp"
+#include "wave_prims.hpp"
 
 namespace sks {
 
@@ -64,34 +64,24 @@ constexpr uint32_t kIdxMask = (1u << kIdxBits) - 1;
 constexpr uint32_t kTFree = 0xFFFFFFFFu;
 static_assert(kGCap <= (1u << kIdxBits), "element index must fit the slot word");
 
-// inclusive prefix sum over the 64 lanes of a wave (DPP; no LDS)
-__device__ __forceinline__ uint32_t wave_scan(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31
-  return v;
-}
-
 // dedup table slot and tag of a value: independent of the top bits of kv_mix
 // (the bucket, and the slow path's slices)
-template <int EW>
 __device__ __forceinline__ uint32_t dd_slot(const KV& v) {
-  const uint64_t f = jc::fp_fold<EW>(v);
+  const uint64_t f = jc::fp_fold<2>(v);
   return (((uint32_t)f ^ (uint32_t)(f >> 32)) * 0x27D4EB2Fu) >> (32 - kTabLog);
 }
-template <int EW>
 __device__ __forceinline__ uint32_t dd_tag(const KV& v) {  // 21 bits, never all ones
-  const uint32_t t = (uint32_t)(kv_mix<EW>(v) >> 28) & 0x1FFFFFu;
+  const uint32_t t = (uint32_t)(kv_mix<2>(v) >> 28) & 0x1FFFFFu;
   return t == 0x1FFFFFu ? 0x1FFFFEu : t;
 }
 
-template <int EW>
+// the 128-bit value of LDS element i
 __device__ __forceinline__ KV key_at(const uint64_t* s_key, uint32_t i) {
-  if constexpr (EW == 1) return KV{s_key[i], 0};
-  else return KV{s_key[2 * i], s_key[2 * i + 1]};
+  return KV{s_key[2 * i], s_key[2 * i + 1]};
+}
+__device__ __forceinline__ void key_put(uint64_t* s_key, uint32_t i, const KV& v) {
+  s_key[2 * i] = v.lo;
+  s_key[2 * i + 1] = v.hi;
 }
 
 // Inserts element i (value v) into the dedup table; returns the index of the
@@ -106,16 +96,15 @@ __device__ __forceinline__ KV key_at(const uint64_t* s_key, uint32_t i) {
 // 2047, read and ignored): the two-exit form of this loop (free slot / same
 // value, the entry assigned at each exit) was miscompiled by ROCm 7.2 for
 // gfx950 in round 3 (reproducer in tools/microbench/chain_exits.hip).
-template <int EW>
 __device__ __forceinline__ uint32_t dd_insert(uint32_t* s_tab, const uint64_t* s_key, const KV& v, uint32_t i,
                                               uint32_t base, uint32_t rmask, bool* full) {
-  const uint32_t tag = dd_tag<EW>(v);
+  const uint32_t tag = dd_tag(v);
   const uint32_t word = (tag << kIdxBits) | i;
-  uint32_t h = dd_slot<EW>(v) & rmask, steps = 0;
+  uint32_t h = dd_slot(v) & rmask, steps = 0;
   uint32_t x = atomicCAS(&s_tab[base + h], kTFree, word);
   for (;;) {
-    const KV u = key_at<EW>(s_key, x & kIdxMask);
-    if ((x == kTFree) | (((x >> kIdxBits) == tag) & kv_eq<EW>(u, v)) | (steps > rmask)) break;
+    const KV u = key_at(s_key, x & kIdxMask);
+    if ((x == kTFree) | (((x >> kIdxBits) == tag) & kv_eq<2>(u, v)) | (steps > rmask)) break;
     h = (h + 1) & rmask;
     ++steps;
     x = atomicCAS(&s_tab[base + h], kTFree, word);
@@ -298,54 +287,15 @@ __global__ __launch_bounds__(kPT) void k_gl_pos(const uint64_t* __restrict__ dat
 
 __device__ unsigned long long g_layout_check;  // SKS check build: dedup invariant violations
 
-#ifdef SKS_LAYOUT_STAMPS  // diagnostic build: cycles per k_gl_place phase (thread 0 of each workgroup)
-// slots 0-4: phase cycles, summed in registers and stored per workgroup at the
-// end (no atomics on the timed path); slots 5-9: event counts (atomics, rare)
-constexpr int kMaxStampWgs = 16384;
-__device__ unsigned long long g_layout_stamps[10];
-__device__ unsigned long long g_layout_stamps_wg[kMaxStampWgs * 5];
-#define LSTAMP(i)                                              \
-  do {                                                         \
-    if (threadIdx.x == 0) {                                    \
-      const uint64_t t_ = __builtin_amdgcn_s_memtime();        \
-      st_acc[i] += t_ - st_last;                               \
-      st_last = t_;                                            \
-    }                                                          \
-  } while (0)
-#define LSTAMP_FLUSH()                                                                  \
-  do {                                                                                  \
-    if (threadIdx.x == 0 && blockIdx.x < kMaxStampWgs)                                  \
-      for (int q_ = 0; q_ < 5; ++q_) g_layout_stamps_wg[blockIdx.x * 5 + q_] = st_acc[q_]; \
-  } while (0)
-#else
-#define LSTAMP(i) do {} while (0)
-#define LSTAMP_FLUSH() do {} while (0)
-#endif
-
-#ifndef SKS_PLACE_DIAG
-#define SKS_PLACE_DIAG 0
-#endif
 constexpr int kPB = 256;                     // threads of the placement kernel
-#ifndef SKS_LAYOUT_STAGED
-#define SKS_LAYOUT_STAGED 1  // normal-path emit through an LDS list in place order (coalesced stores)
-#endif
 constexpr int kTPS = kPB / 64;               // threads per sketch in the register path (4)
-#ifndef SKS_LAYOUT_REGPER
-#define SKS_LAYOUT_REGPER 12
-#endif
-constexpr int kRegPer = SKS_LAYOUT_REGPER;   // elements of its sketch per thread held in registers
+constexpr int kRegPer = 12;                  // elements of its sketch per thread held in registers
 constexpr uint32_t kSkCap = kTPS * kRegPer;  // a group with a sketch holding more (48) takes the bucket passes
 constexpr int kSlowPer = kGCap / kPB;        // slice path: slice elements per thread
 constexpr uint32_t kSpt = kTab / kPB;        // table slots per thread in the emit scan (16)
 constexpr uint32_t kMaxRG = 1u << jc::kRGLogMax;
 constexpr int kPassU = 4;                    // bucket passes: 64-element chunks loaded per round
 static_assert(kSpt % 4 == 0, "emit reads the slots as uint4");
-
-__device__ __forceinline__ uint64_t readlane64(uint64_t x, uint32_t l) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, (int)l);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), (int)l);
-  return ((uint64_t)hi << 32) | lo;
-}
 
 // A value group's raw elements, sketch by sketch: lane s of a wave holds
 // sketch s's count gc, the inclusive prefix gend (sketch s holds elements
@@ -422,12 +372,91 @@ __device__ __forceinline__ void group_load(const uint64_t* __restrict__ data, co
     const uint32_t e = sub + kTPS * k;
     v[k] = KV{0, 0};
     if (!g.fat && g.gn <= kGCap && e < g.gc) {
-#if SKS_PLACE_DIAG == 3  // diagnostics: no global loads (values synthesised from the index)
-      v[k] = KV{(g.src + e) * 0x9E3779B97F4A7C15ull, 0};
-#else
       v[k] = kv_load<EW>(data, g.src + e);
-#endif
     }
+  }
+}
+
+// ---- what the two placement kernels (k_gl_place, k_gl_place1) share ---------------------------
+// A workgroup's (block, region) and the layout's geometry, wave-uniform, and
+// the lane's sketch.
+struct PlaceFrame {
+  uint32_t B, gb_log, GB, RG;  // buckets; log2 of, and buckets per value group; groups per region
+  uint32_t blk, r;             // this workgroup's block and region
+  uint32_t s_end;              // sketches of the block (< 64 in the set's last block)
+  uint32_t* boff;              // the block's boff row
+  uint64_t base;               // the block's first entry
+  bool sv;                     // sketch `lane` of the block exists
+  uint64_t stt;                // ... and starts here in data
+};
+// Fills the frame, stores the region size for the join, and stages the
+// region's group starts of every sketch: s_pos[j * 64 + s] = sketch s's start
+// of the region's group j (j <= RG), read after the caller's next barrier.
+__device__ __forceinline__ PlaceFrame place_frame(uint32_t log_b, uint32_t rg, uint32_t count,
+                                                  const uint64_t* __restrict__ starts,
+                                                  const uint32_t* __restrict__ pos,
+                                                  const uint64_t* __restrict__ bstart,
+                                                  uint32_t* __restrict__ out_boff, uint32_t* s_pos, int tid,
+                                                  int lane) {
+  PlaceFrame f;
+  f.B = 1u << log_b;
+  f.gb_log = jc::lay_gb_log(log_b);
+  f.GB = 1u << f.gb_log;
+  const uint32_t G = f.B >> f.gb_log, NR = jc::lay_regions(log_b, rg), BW = jc::lay_boff_words(log_b);
+  f.RG = (1u << jc::lay_rb_log(log_b, rg)) >> f.gb_log;
+  f.blk = blockIdx.x / NR;
+  f.r = blockIdx.x % NR;
+  f.s_end = min((uint32_t)kTile, count - kTile * f.blk);
+  f.boff = out_boff + (uint64_t)f.blk * BW;
+  if (f.r == 0 && tid == 0) f.boff[BW - 1] = jc::lay_rb_log(log_b, rg);  // the join reads the region size here
+  f.base = bstart[f.blk];
+  f.sv = (uint32_t)lane < f.s_end;
+  f.stt = f.sv ? starts[kTile * f.blk + lane] : 0;
+  for (uint32_t q = tid; q < (f.RG + 1) * kTile; q += kPB) {
+    const uint32_t j = q / kTile, s = q % kTile;
+    s_pos[q] = s < f.s_end ? pos[(uint64_t)(kTile * f.blk + s) * (G + 1) + f.r * f.RG + j] : 0;
+  }
+  return f;
+}
+// the region's entries start at its raw offset in the block
+__device__ __forceinline__ uint32_t place_cursor(const PlaceFrame& f, const uint32_t* s_pos, int lane) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)wave_scan(f.sv ? s_pos[lane] : 0u), 63);
+}
+// Visits every element of a group (coalesced loads, kPassU chunks of 64 per
+// wave and round): fn(value, sketch slot).
+template <int EW, class Fn>
+__device__ __forceinline__ void for_each_elem(const GroupMap& m, const uint64_t* __restrict__ data, int lane,
+                                              int wave, Fn&& fn) {
+  for (uint32_t c0 = (uint32_t)wave * 64; c0 < m.gn; c0 += kPB * kPassU) {
+    KV x[kPassU];
+    uint32_t o[kPassU];
+#pragma unroll
+    for (int u = 0; u < kPassU; ++u) {
+      const uint32_t b = c0 + u * kPB;
+      o[u] = 0;
+      x[u] = KV{0, 0};
+      if (b < m.gn) {
+        const uint64_t at = elem_at(m, b, lane, &o[u]);
+        if (b + (uint32_t)lane < m.gn) x[u] = kv_load<EW>(data, at);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kPassU; ++u)
+      if (c0 + u * kPB + (uint32_t)lane < m.gn) fn(x[u], o[u]);
+  }
+}
+// The region's end, and the largest block-bucket: one word for every
+// workgroup; the stat only grows, so a workgroup whose maximum is not above
+// the value it reads skips the atomic (one word takes ~88 atomics per
+// microsecond)
+__device__ __forceinline__ void place_finish(const PlaceFrame& f, uint32_t cur, uint32_t maxb,
+                                             uint32_t* __restrict__ stat, int tid, int lane, int wave) {
+  if (tid == 0) f.boff[f.B + f.r] = cur;
+  if (wave == 0) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) maxb = max(maxb, (uint32_t)__shfl_xor(maxb, o, 64));
+    if (lane == 0 && maxb && maxb > __hip_atomic_load(stat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+      atomicMax(stat, maxb);
   }
 }
 
@@ -437,7 +466,6 @@ __device__ __forceinline__ void group_load(const uint64_t* __restrict__ data, co
 // of the occupied counts gives every entry its place at the cursor; the
 // entries {value, mask} are written and the masks cleared for the next pass.
 // Two barriers.
-template <int EW>
 __device__ __forceinline__ void emit_pass(uint32_t* s_tab, const uint64_t* s_key, unsigned long long* s_msk,
                                           uint32_t* s_wsum, uint32_t* boff_b0, uint32_t nb, uint32_t pl,
                                           uint64_t base, uint64_t* __restrict__ out_vals,
@@ -482,10 +510,8 @@ __device__ __forceinline__ void emit_pass(uint32_t* s_tab, const uint64_t* s_key
     const uint32_t i = s_tab[e];
     s_tab[e] = kTFree;
     const uint64_t o = base + cur + e;
-#if SKS_PLACE_DIAG != 4  // (diagnostics 4: no global stores)
-    kv_store<EW>(out_vals, o, key_at<EW>(s_key, i));
+    kv_store<2>(out_vals, o, key_at(s_key, i));
     out_masks[o] = s_msk[i];
-#endif
     s_msk[i] = 0;
   }
   // the largest bucket (entries): the occupied counts of its region's threads
@@ -520,7 +546,7 @@ __device__ __forceinline__ void emit_pass(uint32_t* s_tab, const uint64_t* s_key
 // elements (adversarial values only) takes the slice path: hash slices of the
 // group gathered from the sketches, each deduplicated and written in slice
 // order (a slice still above gcap is split in two).  Exact for any input.
-template <int EW, bool CHECK>
+template <bool CHECK>
 __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ data,
                                                   const uint64_t* __restrict__ starts, uint32_t count,
                                                   uint32_t log_b, const uint32_t* __restrict__ pos,
@@ -529,7 +555,7 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
                                                   unsigned long long* __restrict__ out_masks,
                                                   uint32_t* __restrict__ out_boff, uint32_t* __restrict__ stat,
                                                   uint32_t gcap, uint32_t rg) {
-  __shared__ uint64_t s_key[kGCap * EW];
+  __shared__ uint64_t s_key[kGCap * 2];
   __shared__ unsigned long long s_msk[kGCap];
   __shared__ uint32_t s_tab[kTab];
   __shared__ uint32_t s_pos[(kMaxRG + 1) * kTile];  // [j * 64 + s]: sketch s's start of the region's group j
@@ -538,43 +564,24 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
   __shared__ uint32_t s_bcnt[1u << jc::kGLog];
   __shared__ uint32_t s_full, s_pcnt, s_gd, s_qn, s_qd;
   __shared__ unsigned long long s_stk[2 * 72];  // slice path: (slice prefix, level) work stack (prefixes up to 64 bits)
-#if SKS_LAYOUT_STAGED
   __shared__ uint16_t s_stage[kGCap];  // normal-path emit: the group's entries' element indices, in place order
-#endif
 
-  const uint32_t B = 1u << log_b, gb_log = jc::lay_gb_log(log_b), GB = 1u << gb_log;
-  const uint32_t G = B >> gb_log, NR = jc::lay_regions(log_b, rg), BW = jc::lay_boff_words(log_b);
-  const uint32_t RG = (1u << jc::lay_rb_log(log_b, rg)) >> gb_log;
-  const uint32_t blk = blockIdx.x / NR, r = blockIdx.x % NR;
   // the wave index in an SGPR: the per-wave loop bounds stay scalar
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef SKS_LAYOUT_STAMPS
-  uint64_t st_last = __builtin_amdgcn_s_memtime();
-  uint64_t st_acc[5] = {0, 0, 0, 0, 0};
-#endif
-  const uint32_t s_end = min((uint32_t)kTile, count - kTile * blk);
-  uint32_t* boff = out_boff + (uint64_t)blk * BW;
-  if (r == 0 && threadIdx.x == 0) boff[BW - 1] = jc::lay_rb_log(log_b, rg);  // the join reads the region size here
-  const uint64_t base = bstart[blk];
-  const bool sv = (uint32_t)lane < s_end;
-  const uint64_t stt = sv ? starts[kTile * blk + lane] : 0;
-  for (uint32_t q = tid; q < (RG + 1) * kTile; q += kPB) {
-    const uint32_t j = q / kTile, s = q % kTile;
-    s_pos[q] = s < s_end ? pos[(uint64_t)(kTile * blk + s) * (G + 1) + r * RG + j] : 0;
-  }
+  const PlaceFrame pf = place_frame(log_b, rg, count, starts, pos, bstart, out_boff, s_pos, tid, lane);
+  const uint32_t gb_log = pf.gb_log, GB = pf.GB, RG = pf.RG, r = pf.r;
+  uint32_t* const boff = pf.boff;
+  const uint64_t base = pf.base;
   for (uint32_t q = tid; q < kTab / 4; q += kPB)
     reinterpret_cast<uint4*>(s_tab)[q] = make_uint4(kTFree, kTFree, kTFree, kTFree);
   for (uint32_t q = tid; q < kGCap / 2; q += kPB) reinterpret_cast<uint4*>(s_msk)[q] = make_uint4(0, 0, 0, 0);
   if (tid == 0) s_full = 0;
   __syncthreads();
-  // the region's entries start at its raw offset in the block
-  uint32_t cur = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan(sv ? s_pos[lane] : 0u), 63);
-  uint32_t maxb = 0;
+  uint32_t cur = place_cursor(pf, s_pos, lane), maxb = 0;
   KV v[kRegPer];
   const uint32_t my_s = (uint32_t)tid / kTPS, sub = (uint32_t)tid % kTPS;  // this thread's sketch
-  GroupView gv = group_view(s_pos, s_pos + kTile, sv, stt, lane, my_s);
-  group_load<EW>(data, gv, sub, v);
-  LSTAMP(0);
+  GroupView gv = group_view(s_pos, s_pos + kTile, pf.sv, pf.stt, lane, my_s);
+  group_load<2>(data, gv, sub, v);
 
   for (uint32_t j = 0; j < RG; ++j) {
     const uint32_t g = r * RG + j;
@@ -585,8 +592,8 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
     bool fetched = false;
     auto load_next = [&]() {
       if (j + 1 < RG) {
-        gv = group_view(s_pos + (j + 1) * kTile, s_pos + (j + 2) * kTile, sv, stt, lane, my_s);
-        group_load<EW>(data, gv, sub, v);
+        gv = group_view(s_pos + (j + 1) * kTile, s_pos + (j + 2) * kTile, pf.sv, pf.stt, lane, my_s);
+        group_load<2>(data, gv, sub, v);
       }
       fetched = true;
     };
@@ -600,15 +607,11 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
 #pragma unroll
       for (int k = 0; k < kRegPer; ++k) {  // P1
         const uint32_t e = sub + kTPS * k, i = gj.gpre + e;
-        if (e < gj.gc) {
-          if constexpr (EW == 1) s_key[i] = v[k].lo;
-          else { s_key[2 * i] = v[k].lo; s_key[2 * i + 1] = v[k].hi; }
-        }
+        if (e < gj.gc) key_put(s_key, i, v[k]);
       }
       if ((uint32_t)tid < GB) s_bcnt[tid] = 0;
       load_next();
       __syncthreads();
-      LSTAMP(1);
       // P2 (the values read back from LDS), every element's first probe issued
       // together: keys, first compare-swaps, the named elements' keys; then the
       // (rare) rest of each chain, one exit edge (see dd_insert).  A slot word
@@ -624,9 +627,9 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
         w[k] = kTFree;
         h[k] = 0;
         if (e < gj.gc) {
-          const KV x = key_at<EW>(s_key, i);
+          const KV x = key_at(s_key, i);
           // bucket (top gb_log bits of the mix) and slot in its region (the next rlog bits)
-          h[k] = (uint32_t)(kv_mix<EW>(x) >> (64 - kTabLog));
+          h[k] = (uint32_t)(kv_mix<2>(x) >> (64 - kTabLog));
           w[k] = atomicCAS(&s_tab[h[k]], kTFree, i);
         }
       }
@@ -635,21 +638,21 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
         const uint32_t e = sub + kTPS * k, i = gj.gpre + e;
         rep[k] = kTFree;
         if (e < gj.gc) {
-          const KV x = key_at<EW>(s_key, i);
+          const KV x = key_at(s_key, i);
           const uint32_t rbase = h[k] & ~rmask;
           uint32_t hh = h[k] & rmask, xw = w[k], steps = 0;
-          KV u = key_at<EW>(s_key, xw & kIdxMask);
+          KV u = key_at(s_key, xw & kIdxMask);
           for (;;) {
-            if ((xw == kTFree) | kv_eq<EW>(u, x) | (steps > rmask)) break;
+            if ((xw == kTFree) | kv_eq<2>(u, x) | (steps > rmask)) break;
             hh = (hh + 1) & rmask;
             ++steps;
             xw = atomicCAS(&s_tab[rbase + hh], kTFree, i);
-            u = key_at<EW>(s_key, xw & kIdxMask);
+            u = key_at(s_key, xw & kIdxMask);
           }
           const bool f = steps > rmask;  // (an overflowed region names a foreign entry: the group is redone)
           full |= f;
           const uint32_t ri = xw == kTFree ? i : xw;
-          if (CHECK && !f && !kv_eq<EW>(key_at<EW>(s_key, ri), x)) atomicAdd(&g_layout_check, 1ull);
+          if (CHECK && !f && !kv_eq<2>(key_at(s_key, ri), x)) atomicAdd(&g_layout_check, 1ull);
           atomicOr(&s_msk[ri], 1ull << my_s);
           if (xw == kTFree) {  // the representative: its slot (freed at emit) and its place in the bucket
             const uint32_t bk = h[k] >> rlog;
@@ -660,7 +663,6 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
       }
       if (full) s_full = 1;
       __syncthreads();
-      LSTAMP(2);
       if (s_full == 0) {
         // P3: bucket starts from the counts; P4: every representative writes its
         // entry {value, mask} and frees its slot and mask
@@ -673,7 +675,6 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
           maxb = max(maxb, c);
         }
         if ((uint32_t)tid < GB) boff[g * GB + tid] = cur + pre[tid];
-#if SKS_LAYOUT_STAGED
         // representatives list their element at its place (and free their slot);
         // the group's entries then leave with coalesced stores
 #pragma unroll
@@ -686,24 +687,10 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
         for (uint32_t e = (uint32_t)tid; e < tot; e += kPB) {
           const uint32_t i = s_stage[e];
           const uint64_t o = base + cur + e;
-          kv_store<EW>(out_vals, o, key_at<EW>(s_key, i));
+          kv_store<2>(out_vals, o, key_at(s_key, i));
           out_masks[o] = s_msk[i];
           s_msk[i] = 0;
         }
-#else
-#pragma unroll
-        for (int k = 0; k < kRegPer; ++k) {
-          if (rep[k] == kTFree) continue;
-          const uint32_t i = gj.gpre + sub + kTPS * k;
-          const uint64_t o = base + cur + pre[rep[k] >> 12] + (rep[k] & 4095u);
-#if SKS_PLACE_DIAG != 4  // (diagnostics 4: no global stores)
-          kv_store<EW>(out_vals, o, key_at<EW>(s_key, i));
-          out_masks[o] = s_msk[i];
-#endif
-          s_msk[i] = 0;
-          s_tab[h[k]] = kTFree;
-        }
-#endif
         cur += tot;
         done = true;
       } else {  // a bucket region overflowed: clean up, place the group in bucket passes
@@ -713,36 +700,16 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
         __syncthreads();
         if (tid == 0) s_full = 0;
       }
-      LSTAMP(3);
     }
     if (!fetched) load_next();
     if (!done) {
       // ---- bucket passes ------------------------------------------------------------------------
-      const GroupMap m = group_map(s_pos + j * kTile, s_pos + (j + 1) * kTile, sv, stt, lane);
-      // visits every element of the group (coalesced, kPassU chunks per round): f(value, slot)
-      auto for_each = [&](auto&& f) {
-        for (uint32_t c0 = (uint32_t)wave * 64; c0 < m.gn; c0 += kPB * kPassU) {
-          KV x[kPassU];
-          uint32_t o[kPassU];
-#pragma unroll
-          for (int u = 0; u < kPassU; ++u) {
-            const uint32_t b = c0 + u * kPB;
-            o[u] = 0;
-            x[u] = KV{0, 0};
-            if (b < m.gn) {
-              const uint64_t at = elem_at(m, b, lane, &o[u]);
-              if (b + (uint32_t)lane < m.gn) x[u] = kv_load<EW>(data, at);
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < kPassU; ++u)
-            if (c0 + u * kPB + (uint32_t)lane < m.gn) f(x[u], o[u]);
-        }
-      };
+      const GroupMap m = group_map(s_pos + j * kTile, s_pos + (j + 1) * kTile, pf.sv, pf.stt, lane);
+      auto for_each = [&](auto&& fn) { for_each_elem<2>(m, data, lane, wave, fn); };
       __syncthreads();
       if ((uint32_t)tid < GB) s_bcnt[tid] = 0;
       __syncthreads();
-      for_each([&](const KV& x, uint32_t) { atomicAdd(&s_bcnt[kv_group_bucket<EW>(x, gb_log)], 1u); });
+      for_each([&](const KV& x, uint32_t) { atomicAdd(&s_bcnt[kv_group_bucket<2>(x, gb_log)], 1u); });
       __syncthreads();
       bool slices = false;
       for (uint32_t b = 0; b < GB; ++b) slices |= s_bcnt[b] > gcap;
@@ -765,10 +732,9 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
         if (tid == 0) s_pcnt = 0;
         __syncthreads();
         for_each([&](const KV& x, uint32_t o) {
-          if (kv_group_bucket<EW>(x, gb_log) - b0 < b1 - b0) {
+          if (kv_group_bucket<2>(x, gb_log) - b0 < b1 - b0) {
             const uint32_t idx = atomicAdd(&s_pcnt, 1u);
-            if constexpr (EW == 1) s_key[idx] = x.lo;
-            else { s_key[2 * idx] = x.lo; s_key[2 * idx + 1] = x.hi; }
+            key_put(s_key, idx, x);
             s_own[idx] = (uint8_t)o;
           }
         });
@@ -776,12 +742,12 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
         const uint32_t np = s_pcnt, rlog = kTabLog - pl;
         bool full = false;
         for (uint32_t i = tid; i < np; i += kPB) {
-          const KV x = key_at<EW>(s_key, i);
+          const KV x = key_at(s_key, i);
           bool f = false;
-          const uint32_t ri = dd_insert<EW>(s_tab, s_key, x, i, (kv_group_bucket<EW>(x, gb_log) - b0) << rlog,
+          const uint32_t ri = dd_insert(s_tab, s_key, x, i, (kv_group_bucket<2>(x, gb_log) - b0) << rlog,
                                             (1u << rlog) - 1, &f);
           full |= f;
-          if (CHECK && !f && !kv_eq<EW>(key_at<EW>(s_key, ri), x)) atomicAdd(&g_layout_check, 1ull);
+          if (CHECK && !f && !kv_eq<2>(key_at(s_key, ri), x)) atomicAdd(&g_layout_check, 1ull);
           atomicOr(&s_msk[ri], 1ull << s_own[i]);
         }
         if (full) s_full = 1;
@@ -795,14 +761,14 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
           one_bucket = true;
           continue;
         }
-        emit_pass<EW>(s_tab, s_key, s_msk, s_wsum, boff + g * GB + b0, b1 - b0, pl, base, out_vals, out_masks, cur,
+        emit_pass(s_tab, s_key, s_msk, s_wsum, boff + g * GB + b0, b1 - b0, pl, base, out_vals, out_masks, cur,
                       maxb, tid, lane, wave);
         b0 = b1;
       }
       if (slices) {
         // ---- slice path: hash slices of the group, gathered from the sketches -----------------
-        const uint32_t glo = sv ? s_pos[j * kTile + lane] : 0;
-        const uint32_t ghi = sv ? max(s_pos[(j + 1) * kTile + lane], glo) : 0;
+        const uint32_t glo = pf.sv ? s_pos[j * kTile + lane] : 0;
+        const uint32_t ghi = pf.sv ? max(s_pos[(j + 1) * kTile + lane], glo) : 0;
         uint32_t lvl0 = max(gb_log, 1u);
         while (lvl0 < 32 && ((uint64_t)gn_j >> (lvl0 - 1)) > gcap / 2) ++lvl0;
         uint32_t bk_cur = ~0u, bk_start = cur;
@@ -830,16 +796,15 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
             for (uint32_t i = tid; i < kTab / 4; i += kPB)
               reinterpret_cast<uint4*>(s_tab)[i] = make_uint4(kTFree, kTFree, kTFree, kTFree);
             __syncthreads();
-            for (uint32_t s = wave; s < s_end; s += kPB / 64) {
+            for (uint32_t s = wave; s < pf.s_end; s += kPB / 64) {
               const uint32_t a = __shfl(glo, s), b = __shfl(ghi, s);
-              const uint64_t sts = __shfl(stt, s);
+              const uint64_t sts = __shfl(pf.stt, s);
               for (uint32_t e = a + lane; e < b; e += 64) {
-                const KV x = kv_load<EW>(data, sts + e);
-                if ((kv_mix<EW>(x) >> (64 - lvl)) == q) {
+                const KV x = kv_load<2>(data, sts + e);
+                if ((kv_mix<2>(x) >> (64 - lvl)) == q) {
                   const uint32_t idx = atomicAdd(&s_qn, 1u);
                   if (idx < gcap) {
-                    if constexpr (EW == 1) s_key[idx] = x.lo;
-                    else { s_key[2 * idx] = x.lo; s_key[2 * idx + 1] = x.hi; }
+                    key_put(s_key, idx, x);
                     s_own[idx] = (uint8_t)s;
                   }
                 }
@@ -880,10 +845,10 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
               const uint32_t i = tid + k * kPB;
               rp[k] = false;
               if (i < nq) {
-                const KV x = key_at<EW>(s_key, i);
+                const KV x = key_at(s_key, i);
                 bool full_unused = false;  // one region of kTab slots for <= gcap <= kTab / 2 elements
-                const uint32_t ri = dd_insert<EW>(s_tab, s_key, x, i, 0u, kTab - 1, &full_unused);
-                if (CHECK && !kv_eq<EW>(key_at<EW>(s_key, ri), x)) atomicAdd(&g_layout_check, 1ull);
+                const uint32_t ri = dd_insert(s_tab, s_key, x, i, 0u, kTab - 1, &full_unused);
+                if (CHECK && !kv_eq<2>(key_at(s_key, ri), x)) atomicAdd(&g_layout_check, 1ull);
                 atomicOr(&s_msk[ri], 1ull << s_own[i]);
                 rp[k] = ri == i;
               }
@@ -895,7 +860,7 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
               const uint32_t i = tid + k * kPB;
               const uint32_t d = atomicAdd(&s_gd, 1u);
               const uint64_t o = base + cur + d;
-              kv_store<EW>(out_vals, o, key_at<EW>(s_key, i));
+              kv_store<2>(out_vals, o, key_at(s_key, i));
               out_masks[o] = s_msk[i];
             }
             __syncthreads();
@@ -908,24 +873,10 @@ __global__ __launch_bounds__(kPB) void k_gl_place(const uint64_t* __restrict__ d
         for (uint32_t q = tid; q < kTab / 4; q += kPB)
           reinterpret_cast<uint4*>(s_tab)[q] = make_uint4(kTFree, kTFree, kTFree, kTFree);
         for (uint32_t q = tid; q < kGCap / 2; q += kPB) reinterpret_cast<uint4*>(s_msk)[q] = make_uint4(0, 0, 0, 0);
-#ifdef SKS_LAYOUT_STAMPS
-        if (tid == 0) atomicAdd(&g_layout_stamps[8], 1ull);
-#endif
       }
-      LSTAMP(4);
     }
   }
-  if (tid == 0) boff[B + r] = cur;
-  LSTAMP_FLUSH();
-  // the largest block-bucket: one word for every workgroup; the stat only
-  // grows, so a workgroup whose maximum is not above the value it reads skips
-  // the atomic (one word takes ~88 atomics per microsecond)
-  if (wave == 0) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) maxb = max(maxb, (uint32_t)__shfl_xor(maxb, o, 64));
-    if (lane == 0 && maxb && maxb > __hip_atomic_load(stat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      atomicMax(stat, maxb);
-  }
+  place_finish(pf, cur, maxb, stat, tid, lane, wave);
 }
 
 
@@ -939,10 +890,7 @@ constexpr uint32_t kVLog = 8 + jc::kGLog, kVT = 1u << kVLog;  // value slots (20
 constexpr uint32_t kVSpt = kVT / kPB;              // slots per thread in a scan emit (8)
 
 static_assert(kGCap <= kVT, "a normal-path group fits the value table");
-#ifndef SKS_LAYOUT_HALF_AT
-#define SKS_LAYOUT_HALF_AT (kVT / 2)
-#endif
-constexpr uint32_t kHalfAt = SKS_LAYOUT_HALF_AT;   // predicted distinct values above which a group takes two halves
+constexpr uint32_t kHalfAt = kVT / 2;   // predicted distinct values above which a group takes two halves
 static_assert(kVSpt % 2 == 0, "scan emit reads slot pairs");
 
 // Inserts v != 0 into the table region [rbase, rbase + rmask] starting at
@@ -973,10 +921,8 @@ __device__ __forceinline__ bool vp_in(const VPass& p, uint64_t mix) {
   return top - p.q0 < p.span;
 }
 template <bool CHECK>
-#ifndef SKS_LAYOUT_WAVES
-#define SKS_LAYOUT_WAVES 4
-#endif
-__global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(SKS_LAYOUT_WAVES))) void k_gl_place1(const uint64_t* __restrict__ data,
+__global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(4))) void k_gl_place1(
+                                                   const uint64_t* __restrict__ data,
                                                    const uint64_t* __restrict__ starts, uint32_t count,
                                                    uint32_t log_b, const uint32_t* __restrict__ pos,
                                                    const uint64_t* __restrict__ bstart,
@@ -993,29 +939,13 @@ __global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(SKS_LAYOUT_
   __shared__ unsigned long long s_sq[72];     // pass stack: q0
   __shared__ uint32_t s_sl[72];               // pass stack: lvl << 8 | log2(span)
   __shared__ uint32_t s_w8[(1u << jc::kGLog) * (kPB / 64)];  // pass emit: per-bucket wave totals
-#if SKS_LAYOUT_STAGED
   __shared__ uint16_t s_stage[kVT];  // normal-path emit: the group's entries' table slots, in place order
-#endif
 
-  const uint32_t B = 1u << log_b, gb_log = jc::lay_gb_log(log_b), GB = 1u << gb_log;
-  const uint32_t G = B >> gb_log, NR = jc::lay_regions(log_b, rg), BW = jc::lay_boff_words(log_b);
-  const uint32_t RG = (1u << jc::lay_rb_log(log_b, rg)) >> gb_log;
-  const uint32_t blk = blockIdx.x / NR, r = blockIdx.x % NR;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef SKS_LAYOUT_STAMPS
-  uint64_t st_last = __builtin_amdgcn_s_memtime();
-  uint64_t st_acc[5] = {0, 0, 0, 0, 0};
-#endif
-  const uint32_t s_end = min((uint32_t)kTile, count - kTile * blk);
-  uint32_t* boff = out_boff + (uint64_t)blk * BW;
-  if (r == 0 && threadIdx.x == 0) boff[BW - 1] = jc::lay_rb_log(log_b, rg);  // the join reads the region size here
-  const uint64_t base = bstart[blk];
-  const bool sv = (uint32_t)lane < s_end;
-  const uint64_t stt = sv ? starts[kTile * blk + lane] : 0;
-  for (uint32_t q = tid; q < (RG + 1) * kTile; q += kPB) {
-    const uint32_t j = q / kTile, s = q % kTile;
-    s_pos[q] = s < s_end ? pos[(uint64_t)(kTile * blk + s) * (G + 1) + r * RG + j] : 0;
-  }
+  const PlaceFrame pf = place_frame(log_b, rg, count, starts, pos, bstart, out_boff, s_pos, tid, lane);
+  const uint32_t gb_log = pf.gb_log, GB = pf.GB, RG = pf.RG, r = pf.r;
+  uint32_t* const boff = pf.boff;
+  const uint64_t base = pf.base;
   for (uint32_t q = tid; q < kVT / 2; q += kPB) {
     reinterpret_cast<uint4*>(s_vt)[q] = make_uint4(0, 0, 0, 0);
     reinterpret_cast<uint4*>(s_vm)[q] = make_uint4(0, 0, 0, 0);
@@ -1026,15 +956,13 @@ __global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(SKS_LAYOUT_
     s_zero = 0;
   }
   __syncthreads();
-  uint32_t cur = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan(sv ? s_pos[lane] : 0u), 63);
-  uint32_t maxb = 0;
+  uint32_t cur = place_cursor(pf, s_pos, lane), maxb = 0;
   KV v[kRegPer];
   const uint32_t my_s = (uint32_t)tid / kTPS, sub = (uint32_t)tid % kTPS;
   const unsigned long long my_bit = 1ull << my_s;
-  GroupView gv = group_view(s_pos, s_pos + kTile, sv, stt, lane, my_s);
+  GroupView gv = group_view(s_pos, s_pos + kTile, pf.sv, pf.stt, lane, my_s);
   group_load<1>(data, gv, sub, v);
   uint32_t dshare = 1u << 16;  // distinct / raw of the region's last placed group (16.16)
-  LSTAMP(0);
 
   // emit of a pass (thread t reads slots [8 t, 8 t + 8)): the pass's table holds
   // the values of buckets [q0, q0 + span) (a slice of one bucket when span = 1)
@@ -1145,7 +1073,6 @@ __global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(SKS_LAYOUT_
           h[k] = (uint32_t)((gb_log ? m << gb_log : m) >> (64 - kVLog));  // (the bits after the bucket)
           if (e < gj.gc && v[k].lo != 0ull && bk[k] - blo < bn) x0[k] = atomicCAS(&s_vt[h[k]], 0ull, v[k].lo);
         }
-        LSTAMP(1);
         bool full = false;
         uint32_t rep[kRegPer];
 #pragma unroll
@@ -1173,10 +1100,9 @@ __global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(SKS_LAYOUT_
           }
         }
         if (full) atomicAdd(stat + 1, 1u);  // the layout is invalid (the caller retries)
-        LSTAMP(2);
         if (hf + 1 == nh) {  // the next group's loads (in flight during the emit)
           if (j + 1 < RG) {
-            gv = group_view(s_pos + (j + 1) * kTile, s_pos + (j + 2) * kTile, sv, stt, lane, my_s);
+            gv = group_view(s_pos + (j + 1) * kTile, s_pos + (j + 2) * kTile, pf.sv, pf.stt, lane, my_s);
             group_load<1>(data, gv, sub, v);
           }
           fetched = true;
@@ -1192,7 +1118,6 @@ __global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(SKS_LAYOUT_
           maxb = max(maxb, c + (b == 0 ? zero : 0u));
         }
         if ((uint32_t)tid < bn) boff[g * GB + blo + tid] = cur + (tid == 0 ? 0u : pre[blo + tid]);
-#if SKS_LAYOUT_STAGED
         // each representative lists its table slot at its place; then the group's
         // entries leave with coalesced stores (a wave writes 512 contiguous bytes
         // of values and of masks) instead of one scattered 8-byte store each
@@ -1214,26 +1139,8 @@ __global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(SKS_LAYOUT_
             s_vm[slot] = 0ull;
           }
         }
-#else
-#pragma unroll
-        for (int k = 0; k < kRegPer; ++k) {
-          if (rep[k] == kTFree) continue;
-          const uint64_t o = base + cur + pre[rep[k] >> 12] + (rep[k] & 4095u);
-#if SKS_PLACE_DIAG != 4
-          out_vals[o] = s_vt[h[k]];
-          out_masks[o] = s_vm[h[k]];
-#endif
-          s_vt[h[k]] = 0ull;
-          s_vm[h[k]] = 0ull;
-        }
-        if (tid == 0 && zero) {
-          out_vals[base + cur] = 0ull;
-          out_masks[base + cur] = s_zero;
-        }
-#endif
         cur += tot;
         dsum += tot;
-        LSTAMP(3);
         __syncthreads();  // counts and s_zero read; the table is free again
         if ((uint32_t)tid < GB) s_bcnt[tid] = 0;
         if (tid == 0) s_zero = 0;
@@ -1242,7 +1149,7 @@ __global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(SKS_LAYOUT_
       done = true;
     }
     if (!fetched && j + 1 < RG) {
-      gv = group_view(s_pos + (j + 1) * kTile, s_pos + (j + 2) * kTile, sv, stt, lane, my_s);
+      gv = group_view(s_pos + (j + 1) * kTile, s_pos + (j + 2) * kTile, pf.sv, pf.stt, lane, my_s);
       group_load<1>(data, gv, sub, v);
     }
     if (!done) {
@@ -1252,13 +1159,7 @@ __global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(SKS_LAYOUT_
       // (more than 2048 distinct values) is split (buckets into halves, then a
       // bucket into hash slices), depth first, so entries come out in bucket and
       // slice order
-      const GroupMap m = group_map(s_pos + j * kTile, s_pos + (j + 1) * kTile, sv, stt, lane);
-#ifdef SKS_LAYOUT_STAMPS
-      if (tid == 0) {
-        atomicAdd(&g_layout_stamps[8], 1ull);
-        atomicAdd(&g_layout_stamps[gj.fat ? 5 : gn_j > gcap ? 6 : 7], 1ull);
-      }
-#endif
+      const GroupMap m = group_map(s_pos + j * kTile, s_pos + (j + 1) * kTile, pf.sv, pf.stt, lane);
       __syncthreads();
       if (tid == 0) {
         uint32_t parts = 1;  // predicted distinct values (raw x the running distinct share) per part <= 1536
@@ -1284,40 +1185,23 @@ __global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(SKS_LAYOUT_
         __syncthreads();
         if (tid == 0) s_sd = depth - 1;
         bool full = false;
-        for (uint32_t c0 = (uint32_t)wave * 64; c0 < m.gn; c0 += kPB * kPassU) {
-          KV x[kPassU];
-          uint32_t o[kPassU];
-#pragma unroll
-          for (int u = 0; u < kPassU; ++u) {
-            const uint32_t b = c0 + u * kPB;
-            o[u] = 0;
-            x[u] = KV{0, 0};
-            if (b < m.gn) {
-              const uint64_t at = elem_at(m, b, lane, &o[u]);
-              if (b + (uint32_t)lane < m.gn) x[u] = kv_load<1>(data, at);
-            }
+        for_each_elem<1>(m, data, lane, wave, [&](const KV& x, uint32_t o) {
+          const uint64_t mx = kv_mix<1>(x);
+          if (!vp_in(p, mx)) return;
+          if (x.lo == 0ull) {
+            atomicOr(&s_zero, 1ull << o);
+            return;
           }
-#pragma unroll
-          for (int u = 0; u < kPassU; ++u) {
-            if (c0 + u * kPB + (uint32_t)lane >= m.gn) continue;
-            const uint64_t mx = kv_mix<1>(x[u]);
-            if (!vp_in(p, mx)) continue;
-            if (x[u].lo == 0ull) {
-              atomicOr(&s_zero, 1ull << o[u]);
-              continue;
-            }
-            const uint32_t h0 = (uint32_t)((p.lvl ? mx << p.lvl : mx) >> (64 - kVLog));
-            bool claimed;
-            const uint32_t slot = vt_insert(s_vt, x[u].lo, 0u, h0, kVT - 1, atomicCAS(&s_vt[h0], 0ull, x[u].lo),
-                                            &claimed);
-            if (slot == ~0u) {
-              full = true;
-              continue;
-            }
-            if (CHECK && s_vt[slot] != x[u].lo) atomicAdd(&g_layout_check, 1ull);
-            atomicOr(&s_vm[slot], 1ull << o[u]);
+          const uint32_t h0 = (uint32_t)((p.lvl ? mx << p.lvl : mx) >> (64 - kVLog));
+          bool claimed;
+          const uint32_t slot = vt_insert(s_vt, x.lo, 0u, h0, kVT - 1, atomicCAS(&s_vt[h0], 0ull, x.lo), &claimed);
+          if (slot == ~0u) {
+            full = true;
+            return;
           }
-        }
+          if (CHECK && s_vt[slot] != x.lo) atomicAdd(&g_layout_check, 1ull);
+          atomicOr(&s_vm[slot], 1ull << o);
+        });
         if (full) s_full = 1;
         __syncthreads();
         if (s_full) {  // split the pass: halves of its buckets, or two hash slices of its bucket
@@ -1327,9 +1211,6 @@ __global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(SKS_LAYOUT_
           }
           __syncthreads();
           if (tid == 0) {
-#ifdef SKS_LAYOUT_STAMPS
-            atomicAdd(&g_layout_stamps[9], 1ull);
-#endif
             s_full = 0;
             s_zero = 0;
             const uint32_t d = s_sd;
@@ -1361,17 +1242,9 @@ __global__ __launch_bounds__(kPB) __attribute__((amdgpu_waves_per_eu(SKS_LAYOUT_
         if (p.span == 1) maxb = max(maxb, cur - bk_start);
       }
       dshare = (uint32_t)(((uint64_t)(cur - cur0) << 16) / gn_j);
-      LSTAMP(4);
     }
   }
-  if (tid == 0) boff[B + r] = cur;
-  LSTAMP_FLUSH();
-  if (wave == 0) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) maxb = max(maxb, (uint32_t)__shfl_xor(maxb, o, 64));
-    if (lane == 0 && maxb && maxb > __hip_atomic_load(stat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      atomicMax(stat, maxb);
-  }
+  place_finish(pf, cur, maxb, stat, tid, lane, wave);
 }
 
 }  // namespace
@@ -1443,10 +1316,7 @@ hipError_t join_layout_build(const uint64_t* data, const uint64_t* starts, const
   // in every sketch, then the placement: a workgroup per (block, region)
   const uint32_t nb_bounds = d_bounds ? 0 : (G + 1 + kPT / 64 - 1) / (kPT / 64);
   const uint64_t* bounds = d_bounds ? d_bounds : bounds_tmp;
-  // region size: 8 groups when the grid fills the chip at 8 groups per
-  // workgroup (1024 or more workgroups), else fewer, down to 2, so a small
-  // build (a rank's own blocks, config 5's four blocks) is not one long
-  // sequence of groups per workgroup on a few CUs (SKS_LAYOUT_RG forces one)
+  // the region size (join_layout_region_log)
   // (blocks_hint: the blocks that hold sketches, when many are empty — a rank's
   // exchange buffer — so the region size fits the work, not the row count)
   const uint32_t rg = join_layout_region_log(blocks_hint ? std::min(blocks_hint, n_blk) : n_blk, log_b);
@@ -1467,31 +1337,12 @@ hipError_t join_layout_build(const uint64_t* data, const uint64_t* starts, const
                        bounds_tmp, nb_bounds, out_bstart);
     hipLaunchKernelGGL(k_gl_pos<2>, dim3(count), dim3(kPT), 0, s, data, starts, sizes, count, G, bounds, pos, zs);
     if (check)
-      hipLaunchKernelGGL((k_gl_place<2, true>), grid_place, dim3(kPB), 0, s, data, starts, count, log_b, pos,
+      hipLaunchKernelGGL((k_gl_place<true>), grid_place, dim3(kPB), 0, s, data, starts, count, log_b, pos,
                          out_bstart, out_vals, masks, out_boff, d_stat, group_cap(), rg);
     else
-      hipLaunchKernelGGL((k_gl_place<2, false>), grid_place, dim3(kPB), 0, s, data, starts, count, log_b, pos,
+      hipLaunchKernelGGL((k_gl_place<false>), grid_place, dim3(kPB), 0, s, data, starts, count, log_b, pos,
                          out_bstart, out_vals, masks, out_boff, d_stat, group_cap(), rg);
   }
-#ifdef SKS_LAYOUT_STAMPS
-  {
-    unsigned long long h[10] = {0};
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_layout_stamps), sizeof h);
-    const unsigned long long z[10] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_layout_stamps), z, sizeof z);
-    const uint32_t nw = std::min<uint32_t>(grid_place.x, kMaxStampWgs);
-    std::vector<unsigned long long> wg((size_t)nw * 5);
-    (void)hipMemcpyFromSymbol(wg.data(), HIP_SYMBOL(g_layout_stamps_wg), wg.size() * 8);
-    for (uint32_t b = 0; b < nw; ++b)
-      for (int q = 0; q < 5; ++q) h[q] += wg[(size_t)b * 5 + q];
-    const double wgs = (double)nw;
-    fprintf(stderr, "[k_gl_place stamps] cycles per workgroup: setup %.0f load wait+first CAS %.0f chains %.0f "
-            "emit %.0f passes %.0f | groups in passes %llu (fat %llu, above cap %llu, full %llu), "
-            "pass splits %llu (%.0f workgroups)\n",
-            h[0] / wgs, h[1] / wgs, h[2] / wgs, h[3] / wgs, h[4] / wgs, h[8], h[5], h[6], h[7], h[9], wgs);
-  }
-#endif
   return hipGetLastError();
 }
 

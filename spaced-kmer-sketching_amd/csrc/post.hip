@@ -14,8 +14,11 @@
 #include <rocprim/rocprim.hpp>
 #include <rocprim/block/block_radix_sort.hpp>
 
+#include "code_objects.hpp"
+#include "device_mem.hpp"
+#include "post.hpp"
 #include "sks_hash.hpp"
-#include "sks_internal.hpp"
+#include "wave_prims.hpp"
 
 namespace sks {
 
@@ -307,43 +310,6 @@ inline unsigned grid_for(uint64_t n) {
 constexpr int kSelB = 1024;
 constexpr int kSelWaves = kSelB / 64;
 
-// exclusive block scan of a predicate; returns this thread's rank, *total = count
-__device__ __forceinline__ uint32_t block_rank(bool p, uint32_t* wsum, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t bal = __ballot(p);
-  const uint32_t in_wave = (uint32_t)__popcll(bal & ((1ull << lane) - 1));
-  if (lane == 0) wsum[wave] = (uint32_t)__popcll(bal);
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kSelWaves; ++w) {
-    const uint32_t c = wsum[w];
-    before += w < wave ? c : 0u;
-    all += c;
-  }
-  __syncthreads();
-  *total = all;
-  return before + in_wave;
-}
-
-// exclusive block scan of one count per thread (wsum: kSelWaves words)
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t before = inc - v;
-#pragma unroll
-  for (int w = 0; w < kSelWaves; ++w) before += w < wave ? wsum[w] : 0u;
-  __syncthreads();
-  return before;
-}
-
 // Block-wide maximum of one value per thread (wsum64: kSelWaves words).
 __device__ __forceinline__ uint64_t block_max(uint64_t v, uint64_t* wsum64) {
 #pragma unroll
@@ -474,9 +440,11 @@ __global__ __launch_bounds__(kSelB) void k_bottom_select(const uint64_t* __restr
     const uint64_t v = i < n ? f[i] & sel.pmask : ~0ull;
     const bool eq = i < n && !sel.whole && v == sel.prefix;
     uint32_t eq_tot, keep_tot;
-    const uint32_t eq_rank = eq_base + block_rank(eq, wsum, &eq_tot);
+    const uint32_t eq_rank = eq_base + block_rank<kSelWaves>(eq, wsum, &eq_tot);
+    __syncthreads();
     const bool keep = i < n && (v < sel.prefix || (v == sel.prefix && (sel.whole || eq_rank < sel.kk)));
-    const uint32_t pos = out_base + block_rank(keep, wsum, &keep_tot);
+    const uint32_t pos = out_base + block_rank<kSelWaves>(keep, wsum, &keep_tot);
+    __syncthreads();
     if (keep) dst[pos] = uk[b + i];
     eq_base += eq_tot;
     out_base += keep_tot;
@@ -495,16 +463,9 @@ __global__ __launch_bounds__(kSelB) void k_bottom_select(const uint64_t* __restr
 // largest genome, so that padding is not sorted (pads cost as much as keys).
 constexpr uint32_t kFuseMaxItems = 16;
 constexpr uint32_t kFuseCap = kSelB * kFuseMaxItems;  // 16384 candidates
-#ifndef SKS_FUSE_RADIX_BITS
-#define SKS_FUSE_RADIX_BITS 0
-#endif
-#ifndef SKS_FUSE_RANK
-#define SKS_FUSE_RANK default_for_radix_sort
-#endif
 template <int ITEMS>
 using FuseSort = rocprim::block_radix_sort<unsigned long long, kSelB, ITEMS, rocprim::empty_type, 1, 1,
-                                           SKS_FUSE_RADIX_BITS,
-                                           rocprim::block_radix_rank_algorithm::SKS_FUSE_RANK>;
+                                           0, rocprim::block_radix_rank_algorithm::default_for_radix_sort>;
 // The sort is a counting sort on the top kBkLog bits of the packed keys (4096
 // buckets, four per thread) followed by an insertion sort of each thread's
 // buckets in LDS; rocPRIM's block radix sort — whose LDS exchange is 74% bank
@@ -564,15 +525,6 @@ __device__ __forceinline__ void bucket_sort(uint64_t* b, uint32_t c) {
     if ((uint32_t)i < c) b[i] = r[i];
 }
 
-#ifdef SKS_FUSE_STAMPS  // diagnostic build: cycles from start to the end of each phase (workgroup 0)
-__device__ unsigned long long g_fuse_stamps[10];
-#define FSTAMP(i)                                                                   \
-  do {                                                                              \
-    if (threadIdx.x == 0 && blockIdx.x == 0) g_fuse_stamps[i] = __builtin_amdgcn_s_memtime() - f_t0; \
-  } while (0)
-#else
-#define FSTAMP(i) do {} while (0)
-#endif
 template <int FLAVOUR, int ITEMS>
 __global__ __launch_bounds__(kSelB) void k_bottom_fused(uint64_t* __restrict__ rec,
                                                         const uint64_t* __restrict__ src_off,
@@ -606,9 +558,6 @@ __global__ __launch_bounds__(kSelB) void k_bottom_fused(uint64_t* __restrict__ r
     return;
   }
   const uint32_t n = (uint32_t)n64;  // <= kCap (host-checked: max_cnt or the caps)
-#ifdef SKS_FUSE_STAMPS
-  const uint64_t f_t0 = __builtin_amdgcn_s_memtime();
-#endif
 
   // striped (coalesced) loads: the counting sort takes the keys in any order;
   // blocked order (thread t: positions t * ITEMS ..) starts after the sort
@@ -629,12 +578,10 @@ __global__ __launch_bounds__(kSelB) void k_bottom_fused(uint64_t* __restrict__ r
 #pragma unroll
     for (uint32_t q = 0; q < kBkPer; ++q) sbin[tid * kBkPer + q] = 0;
     __syncthreads();
-    FSTAMP(0);
 #pragma unroll
     for (uint32_t j = 0; j < ITEMS; ++j)
       if (j * kSelB + tid < n) atomicAdd(&sbin[bk_of(k[j])], 1u);
     __syncthreads();
-    FSTAMP(1);
     uint32_t cb[kBkPer], sum = 0, mx = 0;
 #pragma unroll
     for (uint32_t q = 0; q < kBkPer; ++q) {
@@ -682,7 +629,6 @@ __global__ __launch_bounds__(kSelB) void k_bottom_fused(uint64_t* __restrict__ r
       for (uint32_t j = 0; j < ITEMS; ++j)
         if (j * kSelB + tid < n) skeys[atomicAdd(&sbin[bk_of(k[j])], 1u)] = k[j];
       __syncthreads();
-      FSTAMP(2);
       // this thread's buckets are the contiguous range [excl, excl + sum), ~2.7
       // keys per bucket: each bucket is sorted in registers by a sorting network
       // (8 keys, or 16 for the ~0.3% of buckets above 8; kBkMax bounds them)
@@ -698,7 +644,6 @@ __global__ __launch_bounds__(kSelB) void k_bottom_fused(uint64_t* __restrict__ r
         st += c;
       }
       __syncthreads();
-      FSTAMP(3);
 #pragma unroll
       for (uint32_t j = 0; j < ITEMS; ++j) {
         const uint32_t i = tid * ITEMS + j;
@@ -720,7 +665,6 @@ __global__ __launch_bounds__(kSelB) void k_bottom_fused(uint64_t* __restrict__ r
     mine += valid ? 1u : 0u;
     dmask |= (valid ? 0u : 1u) << j;
   }
-  FSTAMP(4);
   uint32_t distinct;
   {
     uint32_t v = mine;
@@ -733,7 +677,6 @@ __global__ __launch_bounds__(kSelB) void k_bottom_fused(uint64_t* __restrict__ r
     for (int w = 0; w < kSelWaves; ++w) distinct += wsum[w];
     __syncthreads();
   }
-  FSTAMP(5);
   if (distinct < s_param && retry_ok[g]) {
     if (tid == 0) {
       res[g] = ~0ull;
@@ -765,7 +708,6 @@ __global__ __launch_bounds__(kSelB) void k_bottom_fused(uint64_t* __restrict__ r
         },
         (uint32_t)lim, mx, hist, s_sel);
   }
-  FSTAMP(6);
   // keep (all distinct) or the selected ones, in k-mer order: the sorted keys,
   // their fmh and validity are in registers in blocked order (thread t holds
   // positions t * ITEMS ..), so two block scans place them — the ties at the
@@ -780,12 +722,14 @@ __global__ __launch_bounds__(kSelB) void k_bottom_fused(uint64_t* __restrict__ r
     lt_m |= (lt ? 1u : 0u) << j;
     eq_m |= (eq ? 1u : 0u) << j;
   }
-  uint32_t eq_rank = block_excl_scan((uint32_t)__builtin_popcount(eq_m), wsum);
+  uint32_t eq_rank = block_excl_scan<kSelWaves>((uint32_t)__builtin_popcount(eq_m), wsum);
+  __syncthreads();
   uint32_t keep_m = lt_m;
 #pragma unroll
   for (uint32_t j = 0; j < ITEMS; ++j)
     if ((eq_m >> j) & 1u) keep_m |= (eq_rank++ < sel.kk ? 1u : 0u) << j;
-  uint32_t pos = block_excl_scan((uint32_t)__builtin_popcount(keep_m), wsum);
+  uint32_t pos = block_excl_scan<kSelWaves>((uint32_t)__builtin_popcount(keep_m), wsum);
+  __syncthreads();
   // the kept keys go through LDS (the sorted keys' array is free again) so the
   // global writes are coalesced and each expansion runs once per kept key
   uint64_t* skept = reinterpret_cast<uint64_t*>(smem);
@@ -794,7 +738,6 @@ __global__ __launch_bounds__(kSelB) void k_bottom_fused(uint64_t* __restrict__ r
     if ((keep_m >> j) & 1u) skept[pos++] = k[j];
   __syncthreads();
   for (uint32_t i = tid; i < (uint32_t)lim; i += kSelB) dst[i] = runs_expand(skept[i], runs);
-  FSTAMP(7);
 }
 
 // ---- FracMinHash of one narrow genome: bucketed sort + unique ---------------------------
@@ -872,28 +815,6 @@ __global__ __launch_bounds__(kFracPartB) void k_frac_partition(const uint64_t* _
   if (over) atomicOr(&state[kFracStateStatus], (uint32_t)kFracStatusBucket);
 }
 
-// exclusive block scan of one count per thread, *total = the sum (wsum: kFracWaves words)
-__device__ __forceinline__ uint32_t frac_excl_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t before = inc - v, all = 0;
-#pragma unroll
-  for (int w = 0; w < kFracWaves; ++w) {
-    before += w < wave ? wsum[w] : 0u;
-    all += wsum[w];
-  }
-  __syncthreads();
-  *total = all;
-  return before;
-}
-
 // The sort and unique of one bucket's n keys at reg[0 .. n), n <= ITEMS * kFracB.
 template <uint32_t ITEMS>
 __device__ __forceinline__ void frac_sort_body(uint64_t* __restrict__ reg, uint32_t n, uint32_t b,
@@ -926,7 +847,8 @@ __device__ __forceinline__ void frac_sort_body(uint64_t* __restrict__ reg, uint3
   for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor(mx, o, 64));
   if ((tid & 63) == 0) wmax[tid >> 6] = mx;
   uint32_t total;
-  const uint32_t excl = frac_excl_scan(sum, wsum, &total);  // its barriers publish wmax
+  const uint32_t excl = block_excl_scan<kFracWaves>(sum, wsum, &total);  // its barrier publishes wmax
+  __syncthreads();
   uint32_t bmax = 0;
 #pragma unroll
   for (int w = 0; w < kFracWaves; ++w) bmax = wmax[w] > bmax ? wmax[w] : bmax;
@@ -979,7 +901,8 @@ __device__ __forceinline__ void frac_sort_body(uint64_t* __restrict__ reg, uint3
     first_m |= (first ? 1u : 0u) << j;
   }
   uint32_t distinct;
-  uint32_t pos = frac_excl_scan((uint32_t)__builtin_popcount(first_m), wsum, &distinct);  // barriers: reads done
+  uint32_t pos = block_excl_scan<kFracWaves>((uint32_t)__builtin_popcount(first_m), wsum, &distinct);
+  __syncthreads();  // every thread has read its keys
 #pragma unroll
   for (uint32_t j = 0; j < ITEMS; ++j)
     if ((first_m >> j) & 1u) skeys[pos++] = k[j];
@@ -1318,16 +1241,6 @@ hipError_t launch_bottom_fused(uint64_t* rec, const uint64_t* d_src_off, const u
     if (a != hipSuccess) return a;
     hipLaunchKernelGGL(kernel, dim3(n_seg), dim3(kSelB), lds, s, rec, d_src_off, d_cnt, d_retry_ok,
                        d_dst_off, s_param, key_bits, runs, kconst, out, d_res, d_cap, set_sizes, set_starts);
-#ifdef SKS_FUSE_STAMPS
-    {
-      unsigned long long h[10] = {0};
-      (void)hipStreamSynchronize(s);
-      (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_fuse_stamps), sizeof h);
-      fprintf(stderr, "[k_bottom_fused stamps] n_seg %u max_cnt %llu: zero %llu count %llu scatter %llu isort %llu "
-              "hash %llu distinct %llu select %llu write %llu\n", n_seg, (unsigned long long)max_cnt, h[0], h[1],
-              h[2], h[3], h[4], h[5], h[6], h[7]);
-    }
-#endif
     return hipGetLastError();
   };
   if (max_cnt <= kSelB * 8)

@@ -34,8 +34,9 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "code_objects.hpp"
+#include "scan.hpp"
 #include "sks_hash.hpp"
-#include "sks_internal.hpp"
 
 namespace sks {
 

@@ -34,7 +34,7 @@ class Carver {
   size_t next_ = 0, end_ = 0;
 };
 
-// The four arrays of a join layout (sks_internal.hpp JoinLayout, format in
+// The four arrays of a join layout (join.hpp JoinLayout, format in
 // join_common.hpp), writable as the layout build needs them.
 struct LayoutArrays {
   uint64_t* vals;

@@ -15,9 +15,10 @@
 
 #include <cstdint>
 
+#include "code_objects.hpp"
+#include "search_kernels.hpp"
 #include "sks.h"
 #include "sks_ani.hpp"
-#include "sks_internal.hpp"
 
 namespace sks {
 

@@ -10,10 +10,20 @@
 #include <string>
 #include <vector>
 
+#include "ani.hpp"
+#include "code_objects.hpp"
+#include "device_mem.hpp"
+#include "downsample.hpp"
+#include "ingress.hpp"
+#include "intersect.hpp"
+#include "join.hpp"
+#include "post.hpp"
+#include "scan.hpp"
 #include "scratch_carve.hpp"
+#include "search_kernels.hpp"
 #include "sks.h"
 #include "sks_api_internal.hpp"
-#include "sks_internal.hpp"
+#include "windows.hpp"
 
 #define SKS_HIP(expr)                                                                   \
   do {                                                                                  \

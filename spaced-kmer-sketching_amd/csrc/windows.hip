@@ -27,7 +27,8 @@
 
 #include <cstdint>
 
-#include "sks_internal.hpp"
+#include "code_objects.hpp"
+#include "windows.hpp"
 
 namespace sks {
 

@@ -7,6 +7,7 @@ loaded binary was built from the sources it sits next to."""
 import glob
 import hashlib
 import os
+import re
 import sys
 
 PKG = os.path.dirname(os.path.abspath(__file__))
@@ -20,9 +21,25 @@ def files():
     return sorted(out)
 
 
+def include_closure(roots):
+    """The roots and every file they reach through quoted #include "..." lines
+    that name a file in csrc/ (package-relative paths, sorted)."""
+    seen, todo = set(), list(roots)
+    while todo:
+        rel = todo.pop()
+        if rel in seen:
+            continue
+        seen.add(rel)
+        with open(os.path.join(PKG, rel), encoding="utf-8") as f:
+            for name in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M):
+                if os.path.isfile(os.path.join(PKG, "csrc", name)):
+                    todo.append("csrc/" + name)
+    return sorted(seen)
+
+
 # the sources the fused scan kernel is compiled from (profiles/rNN/traffic.json
 # records this hash; bench.py uses a traffic figure only when it still matches)
-SCAN_FILES = ["csrc/scan.hip", "csrc/sks_hash.hpp", "csrc/sks_internal.hpp"]
+SCAN_FILES = include_closure(["csrc/scan.hip"])
 
 
 def source_hash(rels=None):
@@ -37,7 +54,7 @@ def source_hash(rels=None):
 
 # the sources of the all-pairs join (k_join and its layout build):
 # profiles/rNN/pair_lds.json records this hash
-JOIN_FILES = ["csrc/join.hip", "csrc/join_common.hpp", "csrc/layout.hip", "csrc/sks_internal.hpp"]
+JOIN_FILES = include_closure(["csrc/join.hip", "csrc/layout.hip"])
 
 
 def scan_hash():
