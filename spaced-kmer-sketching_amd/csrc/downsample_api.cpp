@@ -8,18 +8,6 @@
 
 using namespace sks;
 
-namespace {
-
-// The new set while it is being filled: freed on every early return.
-struct SetHolder {
-  sks_sketch_set* set = nullptr;
-  ~SetHolder() {
-    if (set) sks_sketch_set_free(set);
-  }
-};
-
-}  // namespace
-
 extern "C" int sks_sketch_set_downsample(sks_ctx* c, const sks_sketch_set* src, uint64_t param,
                                          sks_sketch_set** out) {
   if (out) *out = nullptr;
@@ -65,24 +53,12 @@ extern "C" int sks_sketch_set_downsample(sks_ctx* c, const sks_sketch_set* src, 
   const int mode = !bottom ? (param == pol.param ? kDownsampleAll : kDownsampleFrac)
                            : (selects ? kDownsampleFlag : kDownsampleAll);
 
-  SetHolder hold;
-  hold.set = new (std::nothrow) sks_sketch_set();
-  if (!hold.set) return sks::fail(SKS_E_NOMEM, "sks_sketch_set_downsample: out of memory");
-  sks_sketch_set* set = hold.set;
-  set->device = c->device;
-  set->elem_words = ew;
-  set->n = n;
-  set->windows = src->windows;
-  set->window = src->window;
-  set->mask[0] = src->mask[0];
-  set->mask[1] = src->mask[1];
-  set->policy = pol;
-  set->policy.param = param;
-  set->names = src->names;
-  set->sizes.assign(n, 0);  // what release_set_arrays sizes d_data by, should a step below fail
-  set->starts.assign(n, 0);
-  SKS_TRY(alloc_u64(&set->d_starts, n));
-  SKS_HIP(dev_alloc(reinterpret_cast<void**>(&set->d_sizes), std::max<uint32_t>(n, 1) * sizeof(uint32_t)));
+  // the device writes d_starts and d_sizes; the host sizes follow the read-back below
+  sks_policy coarser = pol;
+  coarser.param = param;
+  SetPtr set;
+  SKS_TRY(make_sketch_set(c->device, ew, src->window, src->mask, coarser, std::vector<uint32_t>(n, 0), src->windows,
+                          src->names, nullptr, st, MetaUpload::kNone, &set));
 
   MetaArena arena(c);
   const size_t o_chunk = arena.add(chunk_off), o_dense = arena.add(dense_off);
@@ -93,9 +69,9 @@ extern "C" int sks_sketch_set_downsample(sks_ctx* c, const sks_sketch_set* src, 
   uint64_t* d_offs = reinterpret_cast<uint64_t*>(c->pos.ptr);
 
   DownsampleArgs a{};
-  a.data = src->d_data;
-  a.starts = src->d_starts;
-  a.sizes = src->d_sizes;
+  a.data = src->d_data();
+  a.starts = src->d_starts();
+  a.sizes = src->d_sizes();
   a.chunk_off = arena.ptr(o_chunk);
   a.dense_off = arena.ptr(o_dense);
   a.kconst = sks::fmh_const(src->mask[0], src->mask[1], src->window, pol.nonce, pol.flavour);
@@ -121,11 +97,11 @@ extern "C" int sks_sketch_set_downsample(sks_ctx* c, const sks_sketch_set* src, 
   }
 
   SKS_HIP(sks::downsample_count(a, ew, pol.flavour, mode, n, max_len, d_counts, st));
-  SKS_HIP(sks::downsample_offsets(d_counts, n_chunks, d_offs, a.chunk_off, n, set->d_starts, set->d_sizes, c->tmp,
+  SKS_HIP(sks::downsample_offsets(d_counts, n_chunks, d_offs, a.chunk_off, n, set->d_starts(), set->d_sizes(), c->tmp,
                                   st));
   // the call's one wait: the new sizes size the new set's data array exactly
   std::vector<uint32_t> sizes(n, 0);
-  SKS_HIP(sks::pinned_d2h(sizes.data(), set->d_sizes, n * sizeof(uint32_t), st));
+  SKS_HIP(sks::pinned_d2h(sizes.data(), set->d_sizes(), n * sizeof(uint32_t), st));
   uint64_t total = 0;
   for (uint32_t g = 0; g < n; ++g) {
     if (sizes[g] > src->sizes[g])
@@ -133,10 +109,9 @@ extern "C" int sks_sketch_set_downsample(sks_ctx* c, const sks_sketch_set* src, 
     set->starts[g] = total;
     total += sizes[g];
   }
-  SKS_TRY(alloc_u64(&set->d_data, total * ew));
+  SKS_TRY(alloc_u64(set->data, total * ew, st));
   set->sizes = sizes;
-  SKS_HIP(sks::downsample_scatter(a, ew, pol.flavour, mode, n, max_len, d_offs, set->d_data, st));
-  *out = hold.set;
-  hold.set = nullptr;
+  SKS_HIP(sks::downsample_scatter(a, ew, pol.flavour, mode, n, max_len, d_offs, set->d_data(), st));
+  *out = set.release();
   return SKS_OK;
 }

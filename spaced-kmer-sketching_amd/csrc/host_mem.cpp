@@ -206,9 +206,25 @@ void free_blocks(const std::vector<CachedBlock>& blocks) {
   }
 }
 
+// Parks a block whose last use has completed (ready == null) or completes at
+// the event `ready`; evicts the oldest blocks beyond the cache limits.
+void park(void* p, size_t bytes, hipEvent_t ready) {
+  std::vector<CachedBlock> evict;
+  {
+    std::lock_guard<std::mutex> lk(g_cache_mu);
+    g_cache.push_back({current_device(), p, bytes, ready});
+    while (g_cache.size() > kCacheMaxBlocks ||
+           (g_cache.size() > 1 && cache_bytes_locked() > kCacheMaxBytes)) {
+      evict.push_back(g_cache.front());
+      g_cache.erase(g_cache.begin());
+    }
+  }
+  free_blocks(evict);
+}
+
 }  // namespace
 
-hipError_t dev_alloc(void** p, size_t bytes) {
+hipError_t cache_alloc(void** p, size_t bytes, size_t* real) {
   bytes = std::max<size_t>(bytes, 8);
   const int dev = current_device();
   {
@@ -229,6 +245,7 @@ hipError_t dev_alloc(void** p, size_t bytes) {
     }
     if (best != g_cache.size()) {
       *p = g_cache[best].p;
+      *real = g_cache[best].bytes;
       g_cache.erase(g_cache.begin() + best);
       return hipSuccess;
     }
@@ -239,25 +256,16 @@ hipError_t dev_alloc(void** p, size_t bytes) {
     trim_device_cache(dev);
     e = hipMalloc(p, bytes);
   }
+  *real = e == hipSuccess ? bytes : 0;
   return e;
 }
 
-void dev_release(void* p, size_t bytes, hipEvent_t ready) {
-  if (!p) {
-    if (ready) (void)hipEventDestroy(ready);
-    return;
-  }
-  std::vector<CachedBlock> evict;
-  {
-    std::lock_guard<std::mutex> lk(g_cache_mu);
-    g_cache.push_back({current_device(), p, std::max<size_t>(bytes, 8), ready});
-    while (g_cache.size() > kCacheMaxBlocks ||
-           (g_cache.size() > 1 && cache_bytes_locked() > kCacheMaxBytes)) {
-      evict.push_back(g_cache.front());
-      g_cache.erase(g_cache.begin());
-    }
-  }
-  free_blocks(evict);
+void cache_release(void* p, size_t bytes) {
+  if (p) park(p, bytes, nullptr);
+}
+
+void cache_release_after(void* p, size_t bytes, hipStream_t s) {
+  if (p) park(p, bytes, release_point(s));
 }
 
 void trim_device_cache(int device) {
@@ -275,23 +283,5 @@ void trim_device_cache(int device) {
   }
   free_blocks(drop);
 }
-
-void release_set_arrays(sks_sketch_set* set, hipStream_t stream, bool ordered) {
-  uint64_t total = 0;
-  for (uint32_t v : set->sizes) total += v;
-  void* arrays[3] = {set->d_data, set->d_starts, set->d_sizes};
-  const size_t bytes[3] = {std::max<size_t>(std::max<uint64_t>(total * set->elem_words, 1) * 8, set->data_bytes),
-                           (size_t)std::max<uint32_t>(set->n, 1) * 8,
-                           (size_t)std::max<uint32_t>(set->n, 1) * 4};
-  for (int i = 0; i < 3; ++i)
-    if (arrays[i]) dev_release(arrays[i], bytes[i], ordered ? release_point(stream) : nullptr);
-  set->d_data = nullptr;
-  set->d_starts = nullptr;
-  set->d_sizes = nullptr;
-}
-
-hipError_t cache_alloc(void** p, size_t bytes) { return dev_alloc(p, bytes); }
-
-void cache_release_after(void* p, size_t bytes, hipStream_t s) { dev_release(p, bytes, release_point(s)); }
 
 }  // namespace sks

@@ -1,3 +1,6 @@
+// The sketch file format, host only (the entry points that move sets between a
+// device and files are in sketch_set.cpp).
+//
 // Persisted sketches (no reference equivalent — the
 // reference re-parses and re-sketches every FASTA for each of its 62
 // configurations, kmer-sketching.cpp:168).
@@ -38,8 +41,6 @@
 #include <cstring>
 #include <string>
 #include <vector>
-
-#include <hip/hip_runtime.h>
 
 #include "sks.h"
 #include "sks_api_internal.hpp"
@@ -104,10 +105,6 @@ bool less128(const uint64_t* a, const uint64_t* b, int ew) {
   if (ew == 1) return a[0] < b[0];
   return a[1] < b[1] || (a[1] == b[1] && a[0] < b[0]);
 }
-
-}  // namespace
-
-namespace {
 
 int write_impl(const char* path, const SketchFileMeta& meta, const std::vector<uint32_t>& sizes,
                const std::vector<uint64_t>& windows, const std::vector<SketchGroup>* groups,
@@ -300,190 +297,3 @@ int read_sketch_file_any(const char* path, SketchFileMeta& meta, std::vector<uin
 }
 
 }  // namespace sks
-
-#define SKS_HIP(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return sks::fail(SKS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-  } while (0)
-
-namespace {
-
-// Uploads host sketches into a new device set.
-int make_device_set(int device, const sks::SketchFileMeta& meta, const std::vector<uint32_t>& sizes,
-                    const std::vector<uint64_t>& windows, const uint64_t* host_data,
-                    const uint64_t* device_data, std::vector<std::string> names,
-                    sks_sketch_set** out) {
-  sks_sketch_set* set = new (std::nothrow) sks_sketch_set();
-  if (!set) return sks::fail(SKS_E_NOMEM, "out of memory");
-  set->device = device;
-  set->elem_words = meta.elem_words;
-  set->n = (uint32_t)sizes.size();
-  set->sizes = sizes;
-  set->windows = windows;
-  set->window = meta.window;
-  set->mask[0] = meta.mask[0];
-  set->mask[1] = meta.mask[1];
-  set->policy = meta.policy;
-  set->names = std::move(names);
-  set->starts.resize(set->n);
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < set->n; ++i) {
-    set->starts[i] = total;
-    total += sizes[i];
-  }
-  auto bail = [&](const char* what) {
-    sks_sketch_set_free(set);
-    return sks::fail(SKS_E_HIP, std::string("sketch set: ") + what);
-  };
-  const size_t data_bytes = std::max<uint64_t>(total * meta.elem_words, 1) * 8;
-  if (hipMalloc(reinterpret_cast<void**>(&set->d_data), data_bytes) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&set->d_starts), std::max<uint32_t>(set->n, 1) * 8) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&set->d_sizes), std::max<uint32_t>(set->n, 1) * 4) != hipSuccess)
-    return bail("hipMalloc failed");
-  const size_t words = total * meta.elem_words;
-  if (words && host_data &&
-      hipMemcpy(set->d_data, host_data, words * 8, hipMemcpyHostToDevice) != hipSuccess)
-    return bail("upload failed");
-  if (words && device_data &&
-      hipMemcpy(set->d_data, device_data, words * 8, hipMemcpyDeviceToDevice) != hipSuccess)
-    return bail("device copy failed");
-  if (set->n && (hipMemcpy(set->d_starts, set->starts.data(), set->n * 8, hipMemcpyHostToDevice) != hipSuccess ||
-                 hipMemcpy(set->d_sizes, sizes.data(), set->n * 4, hipMemcpyHostToDevice) != hipSuccess))
-    return bail("metadata upload failed");
-  *out = set;
-  return SKS_OK;
-}
-
-struct DevGuard {
-  int prev = -1;
-  explicit DevGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DevGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
-}  // namespace
-
-extern "C" {
-
-int sks_sketch_set_info(const sks_sketch_set* set, sks_sketch_info* info) {
-  if (!set || !info) return sks::fail(SKS_E_ARG, "sks_sketch_set_info: null argument");
-  info->window = set->window;
-  info->elem_words = set->elem_words;
-  info->mask[0] = set->mask[0];
-  info->mask[1] = set->mask[1];
-  info->policy = set->policy;
-  info->n = set->n;
-  info->has_names = set->names.empty() ? 0 : 1;
-  return SKS_OK;
-}
-
-const char* sks_sketch_set_name(const sks_sketch_set* set, uint32_t i) {
-  if (!set || i >= set->names.size()) return nullptr;
-  return set->names[i].c_str();
-}
-
-int sks_sketch_set_set_names(sks_sketch_set* set, const char* const* names) {
-  if (!set) return sks::fail(SKS_E_ARG, "sks_sketch_set_set_names: null set");
-  std::vector<std::string> v;
-  if (names)
-    for (uint32_t i = 0; i < set->n; ++i) {
-      if (!names[i]) return sks::fail(SKS_E_ARG, "sks_sketch_set_set_names: null name");
-      v.emplace_back(names[i]);
-    }
-  set->names = std::move(v);
-  return SKS_OK;
-}
-
-int sks_sketch_set_save(const sks_sketch_set* set, const char* path) {
-  if (!set || !path) return sks::fail(SKS_E_ARG, "sks_sketch_set_save: null argument");
-  DevGuard g(set->device);
-  uint64_t total = 0;
-  for (uint32_t v : set->sizes) total += v;
-  std::vector<uint64_t> host(total * set->elem_words);
-  if (!host.empty())
-    SKS_HIP(hipMemcpy(host.data(), set->d_data, host.size() * 8, hipMemcpyDeviceToHost));
-  sks::SketchFileMeta meta;
-  meta.window = set->window;
-  meta.elem_words = set->elem_words;
-  meta.mask[0] = set->mask[0];
-  meta.mask[1] = set->mask[1];
-  meta.policy = set->policy;
-  return sks::write_sketch_file(path, meta, set->sizes, set->windows, host.data(), set->names);
-}
-
-int sks_sketch_set_load(sks_ctx* ctx, const char* path, sks_sketch_set** out) {
-  if (!ctx || !path || !out) return sks::fail(SKS_E_ARG, "sks_sketch_set_load: null argument");
-  *out = nullptr;
-  sks::SketchFileMeta meta;
-  std::vector<uint32_t> sizes;
-  std::vector<uint64_t> windows, data;
-  std::vector<std::string> names;
-  int rc = sks::read_sketch_file(path, meta, sizes, windows, data, names);
-  if (rc != SKS_OK) return rc;
-  const int device = sks_ctx_device(ctx);
-  DevGuard g(device);
-  return make_device_set(device, meta, sizes, windows, data.data(), nullptr, std::move(names), out);
-}
-
-int sks_sketch_set_concat(sks_ctx* ctx, const sks_sketch_set* const* sets, uint32_t n_sets,
-                          sks_sketch_set** out) {
-  if (!ctx || !out || (n_sets && !sets)) return sks::fail(SKS_E_ARG, "sks_sketch_set_concat: null argument");
-  *out = nullptr;
-  if (n_sets == 0) return sks::fail(SKS_E_ARG, "sks_sketch_set_concat: no sets");
-  const sks_sketch_set* a = sets[0];
-  bool names = true;
-  for (uint32_t i = 0; i < n_sets; ++i) {
-    const sks_sketch_set* b = sets[i];
-    if (!b) return sks::fail(SKS_E_ARG, "sks_sketch_set_concat: null set");
-    if (b->window != a->window || b->elem_words != a->elem_words || b->mask[0] != a->mask[0] ||
-        b->mask[1] != a->mask[1] || b->policy.kind != a->policy.kind ||
-        b->policy.param != a->policy.param || b->policy.nonce != a->policy.nonce ||
-        b->policy.flavour != a->policy.flavour)
-      return sks::fail(SKS_E_ARG, "sks_sketch_set_concat: sets differ in window, mask or policy");
-    names = names && (b->names.size() == b->n);
-  }
-  const int device = sks_ctx_device(ctx);
-  DevGuard g(device);
-  std::vector<uint32_t> sizes;
-  std::vector<uint64_t> windows;
-  std::vector<std::string> all_names;
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < n_sets; ++i) {
-    sizes.insert(sizes.end(), sets[i]->sizes.begin(), sets[i]->sizes.end());
-    windows.insert(windows.end(), sets[i]->windows.begin(), sets[i]->windows.end());
-    if (names) all_names.insert(all_names.end(), sets[i]->names.begin(), sets[i]->names.end());
-    for (uint32_t v : sets[i]->sizes) total += v;
-  }
-  const int ew = a->elem_words;
-  uint64_t* staged = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&staged), std::max<uint64_t>(total * ew, 1) * 8) != hipSuccess)
-    return sks::fail(SKS_E_HIP, "sks_sketch_set_concat: hipMalloc failed");
-  uint64_t at = 0;
-  for (uint32_t i = 0; i < n_sets; ++i) {
-    uint64_t words = 0;
-    for (uint32_t v : sets[i]->sizes) words += (uint64_t)v * ew;
-    if (words && hipMemcpy(staged + at, sets[i]->d_data, words * 8, hipMemcpyDefault) != hipSuccess) {
-      (void)hipFree(staged);
-      return sks::fail(SKS_E_HIP, "sks_sketch_set_concat: copy failed");
-    }
-    at += words;
-  }
-  sks::SketchFileMeta meta;
-  meta.window = a->window;
-  meta.elem_words = ew;
-  meta.mask[0] = a->mask[0];
-  meta.mask[1] = a->mask[1];
-  meta.policy = a->policy;
-  const int rc = make_device_set(device, meta, sizes, windows, nullptr, staged, std::move(all_names), out);
-  (void)hipFree(staged);
-  return rc;
-}
-
-}  // extern "C"

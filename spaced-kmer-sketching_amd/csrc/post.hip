@@ -41,9 +41,9 @@ hipError_t Scratch::reserve(size_t n) {
   }
   ptr = nullptr;
   bytes = 0;
-  size_t want = std::max<size_t>(std::max<size_t>(n, grown), 1 << 20);
-  hipError_t e = owner ? cache_alloc(&ptr, want) : hipMalloc(&ptr, want);
-  if (e == hipSuccess) bytes = want;
+  size_t want = std::max<size_t>(std::max<size_t>(n, grown), 1 << 20), got = want;
+  hipError_t e = owner ? cache_alloc(&ptr, want, &got) : hipMalloc(&ptr, want);
+  if (e == hipSuccess) bytes = got;  // a parked block's real size: what goes back on the next growth
   return e;
 }
 
@@ -1025,12 +1025,6 @@ hipError_t launch_seg_ids(uint64_t* out, const uint64_t* d_off, uint32_t n_seg, 
   if (n_seg == 0 || max_len == 0) return hipSuccess;
   hipLaunchKernelGGL(k_seg_ids, dim3(grid_for(max_len), n_seg), dim3(kB), 0, s, out, d_off);
   return hipGetLastError();
-}
-
-int seg_tag_bits(uint32_t n_seg) {
-  int b = 0;
-  while (b < 32 && (1ull << b) < n_seg) ++b;
-  return b;
 }
 
 BitRuns bit_runs(uint64_t mask) {

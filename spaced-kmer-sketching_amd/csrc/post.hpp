@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "build_plan.hpp"
 #include "device_mem.hpp"
 
 namespace sks {
@@ -84,7 +85,6 @@ hipError_t launch_frac_fused(const uint64_t* rec, const uint64_t* d_cnt, const u
 hipError_t compact_regions(const uint64_t* src, uint64_t* dst, const uint64_t* d_src_off,
                            const uint64_t* d_dst_off, uint32_t n_seg, uint64_t max_len,
                            hipStream_t s, const BitRuns* pack = nullptr, int tag_shift = -1);
-int seg_tag_bits(uint32_t n_seg);  // ceil(log2(n_seg))
 // out[off[g] .. off[g+1]) = g: the segment of every element (a segment tag
 // that does not fit above the key rides as a sort value instead)
 hipError_t launch_seg_ids(uint64_t* out, const uint64_t* d_off, uint32_t n_seg, uint64_t max_len, hipStream_t s);

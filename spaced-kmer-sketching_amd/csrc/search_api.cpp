@@ -221,7 +221,7 @@ int sks_search_sets(sks_ctx* c, const sks_sketch_set* queries, const sks_sketch_
   const int k = (__builtin_popcountll(qi.mask[0]) + __builtin_popcountll(qi.mask[1])) / 2;
   if (k <= 0) return sks::fail(SKS_E_ARG, "sks_search_sets: the sets' mask selects no position");
   auto side = [](const sks_sketch_set* s) {
-    SearchSide S{s->d_data, s->d_starts, s->d_sizes, s->n, 0, 0, s->sizes.data()};
+    SearchSide S{s->d_data(), s->d_starts(), s->d_sizes(), s->n, 0, 0, s->sizes.data()};
     for (uint32_t v : s->sizes) {
       S.max_size = std::max(S.max_size, v);
       S.total += v;

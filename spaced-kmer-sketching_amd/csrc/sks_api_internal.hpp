@@ -6,25 +6,6 @@
 
 #include "sks.h"
 
-// A device-resident set of sketches (one per genome / segment).
-struct sks_sketch_set {
-  int device = 0;
-  int elem_words = 1;
-  uint32_t n = 0;
-  uint64_t* d_data = nullptr;    // elements (elem_words u64 each)
-  uint64_t* d_starts = nullptr;  // [n] element index of each sketch
-  uint32_t* d_sizes = nullptr;   // [n]
-  size_t data_bytes = 0;         // d_data's allocation when it is larger than the sketches (0: exact)
-  std::vector<uint32_t> sizes;
-  std::vector<uint64_t> starts;
-  std::vector<uint64_t> windows;
-  // how the sketches were made (persisted with them)
-  int window = 0;
-  uint64_t mask[2] = {0, 0};
-  sks_policy policy{};
-  std::vector<std::string> names;  // optional, from a sketch file or sks_sketch_set_set_name
-};
-
 namespace sks {
 
 // Records `msg` as the calling thread's last error and returns `code`.

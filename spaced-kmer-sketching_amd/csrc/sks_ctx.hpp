@@ -1,12 +1,15 @@
 // What the C-ABI translation units that run on a device share (ctx.cpp,
-// host_mem.cpp, build.cpp, pairs.cpp, search_api.cpp, downsample_api.cpp): the context, the error
-// macros, the metadata arena, the device block cache and small argument helpers.
+// host_mem.cpp, sketch_set.cpp, kmer_list.cpp, build.cpp, build_post.cpp,
+// pairs.cpp, search_api.cpp, downsample_api.cpp): the context, the sketch set
+// and k-mer list with the device blocks they own, the error macros, the
+// metadata arena and small argument helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 #include <initializer_list>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -85,12 +88,34 @@ struct sks_ctx {
   }
 };
 
+// A device-resident set of sketches (one per genome / segment).  Its arrays are
+// cached device blocks: a set dropped half-built gives them back by itself.
+struct sks_sketch_set {
+  int device = 0;
+  int elem_words = 1;
+  uint32_t n = 0;
+  sks::DevBlock data;     // elements (elem_words u64 each)
+  sks::DevBlock dstarts;  // [n] u64 element index of each sketch
+  sks::DevBlock dsizes;   // [n] u32
+  uint64_t* d_data() const { return data.as<uint64_t>(); }
+  uint64_t* d_starts() const { return dstarts.as<uint64_t>(); }
+  uint32_t* d_sizes() const { return dsizes.as<uint32_t>(); }
+  std::vector<uint32_t> sizes;
+  std::vector<uint64_t> starts;
+  std::vector<uint64_t> windows;
+  // how the sketches were made (persisted with them)
+  int window = 0;
+  uint64_t mask[2] = {0, 0};
+  sks_policy policy{};
+  std::vector<std::string> names;  // optional, from a sketch file or sks_sketch_set_set_name
+};
+
 struct sks_kmer_list {
   int device = 0;
   uint32_t n = 0;
   uint64_t total = 0;
-  uint64_t* d_pos = nullptr;   // [total] window start byte of each k-mer, stream order
-  uint64_t* d_bits = nullptr;  // [total][4] kmer_bits lo, hi, masked_bits lo, hi
+  sks::DevBlock pos;   // [total] u64 window start byte of each k-mer, stream order
+  sks::DevBlock bits;  // [total][4] u64 kmer_bits lo, hi, masked_bits lo, hi
   std::vector<uint64_t> counts;
 };
 
@@ -148,25 +173,24 @@ inline int end_bit_of(uint64_t max_value) {
   return b < 1 ? 1 : b;
 }
 
-// ---- the device block cache (host_mem.cpp) ------------------------------------------
-// A cached block of at least `bytes` (and at most 2x + 1 MB, so a small request
-// does not pin a large block), or a fresh hipMalloc.
-hipError_t dev_alloc(void** p, size_t bytes);
-// Parks a block whose last use has completed (ready == null; the caller
-// guarantees it, see sks_sketch_set_free) or completes at the event `ready`;
-// evicts the oldest blocks beyond the cache limits (hipFree waits for them).
-void dev_release(void* p, size_t bytes, hipEvent_t ready = nullptr);
-void trim_device_cache(int device);
-// Returns a set's arrays to the block cache: at once (the device is idle for
-// them), or ordered after the current end of `stream`.
-void release_set_arrays(sks_sketch_set* set, hipStream_t stream, bool ordered);
-
-inline int alloc_u64(uint64_t** p, uint64_t words, size_t* bytes_out = nullptr) {
-  const size_t bytes = std::max<uint64_t>(words, 1) * sizeof(uint64_t);
-  SKS_HIP(dev_alloc(reinterpret_cast<void**>(p), bytes));
-  if (bytes_out) *bytes_out = bytes;
+// A block of `words` u64 (at least one) from the block cache, bound to `st`.
+inline int alloc_u64(DevBlock& b, uint64_t words, hipStream_t st) {
+  SKS_HIP(b.alloc(std::max<uint64_t>(words, 1) * sizeof(uint64_t), st));
   return SKS_OK;
 }
+
+// ---- sketch sets (sketch_set.cpp) -------------------------------------------------------
+using SetPtr = std::unique_ptr<sks_sketch_set>;
+// How a new set's d_starts / d_sizes get their contents: written by the device
+// later (the caller then sets the host sizes and starts), uploaded on `st`
+// through the pinned ring without waiting, or with blocking copies.
+enum class MetaUpload { kNone, kStream, kBlocking };
+// The one place that makes a set: fills the host fields (starts from sizes),
+// allocates d_starts and d_sizes and, with `data_words`, d_data of that many
+// words, every block bound to `st`; uploads the metadata as `up` says.
+int make_sketch_set(int device, int elem_words, int window, const uint64_t mask[2], const sks_policy& policy,
+                    std::vector<uint32_t> sizes, std::vector<uint64_t> windows, std::vector<std::string> names,
+                    const uint64_t* data_words, hipStream_t st, MetaUpload up, SetPtr* out);
 
 // ---- argument helpers (ctx.cpp) ---------------------------------------------------------
 // The opening checks of the entry points that take a join layout: a context, a

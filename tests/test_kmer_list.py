@@ -122,6 +122,33 @@ def test_device_list_capacity_rerun(gpu):
 
 
 @pytest.mark.gpu
+def test_list_blocks_recycled_into_sketch_set(gpu):
+    """A freed list's arrays go to the device block cache, not back to the
+    driver: a sketch set built next on the same context may be handed those very
+    blocks.  The set must equal the oracle's sketches all the same, and a second
+    list (which may in turn sit in recycled blocks) the first."""
+    import sksffi
+    torch, ctx = gpu
+    genomes = [_genome(20000, 40 + i) for i in range(2)]
+    stream = b"".join(g.tobytes() + b"\n" for g in genomes)
+    offs = [0, len(genomes[0]) + 1, len(stream)]
+    w, c = 21, 5
+    m = O.mask(w, 21, 1)
+    d = torch.frombuffer(bytearray(stream), dtype=torch.uint8).to("cuda:0")
+    first = ctx.kmer_list(d.data_ptr(), len(stream), offs, w, m, c)  # built, copied, freed
+    ss = ctx.sketch_build(d.data_ptr(), len(stream), offs, w, m, sksffi.SKS_FRAC_MOD, c)
+    for g in range(2):
+        want, nw = O.sketch(O.cut_runs(stream[offs[g]:offs[g + 1]]), w, m, "frac", c)
+        assert np.array_equal(ss.sketch(g), want), f"sketch mismatch on genome {g}"
+        assert int(ss.windows()[g]) == nw
+    again = ctx.kmer_list(d.data_ptr(), len(stream), offs, w, m, c)
+    ss.free()
+    for a, b in zip(first, again):
+        assert np.array_equal(a, b)
+    assert len(first[0]) > 1000 and list(first[2]) == expected(stream, offs, w, m, c)[2]
+
+
+@pytest.mark.gpu
 def test_facade_nucleotide_string_list_to_kmers(tmp_path):
     if not os.path.exists(FACADE):
         subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp")], check=True)
