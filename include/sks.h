@@ -26,7 +26,7 @@ extern "C" {
                               the buckets per region, which the join reads: layouts built by
                               an ABI-2 library (rows without that word) must not be joined by
                               this one (round 5); later additions within 3 (new symbols
-                              only): sks_sketch_set_downsample.  2: deduplicated join layout (masks, region
+                              only): sks_sketch_set_downsample, sks_sketch_set_merge.  2: deduplicated join layout (masks, region
                               ends), elem_words on the layout entry points,
                               sks_ctx_set_join_check; later additions within 2 (new symbols
                               only): sks_ani_rows, sks_intersect_layout_ani, sks_host_alloc,
@@ -215,6 +215,42 @@ int sks_sketch_set_concat(sks_ctx* ctx, const sks_sketch_set* const* sets, uint3
  * of every queued call (sks_ctx_synchronize waits for it; the source set may be
  * freed with sks_sketch_set_free at once). */
 int sks_sketch_set_downsample(sks_ctx* ctx, const sks_sketch_set* set, uint64_t param, sks_sketch_set** out);
+/* Grouped unions: a new set of n_groups sketches on the context's device, sketch
+ * g the union of the source sketches members[group_off[g] .. group_off[g + 1]).
+ * The source sketches are numbered as sks_sketch_set_concat orders them (set
+ * 0's, then set 1's, ...).  group_off has n_groups + 1 non-decreasing entries
+ * from 0; a source sketch may be listed in several groups, in none, or twice in
+ * one; an empty group gives an empty sketch.  Elements are ascending (wide ones
+ * by the 128-bit value) and unique, whatever the order of the members.  As the
+ * elements are masked canonical k-mers kept on their own hash, the union of the
+ * parts' sketches is the sketch of the parts taken together: the result equals
+ * sks_sketch_build of the same sequences with one segment per group (parts
+ * separated so that no window spans two, or cut with (window - 1)-base halos).
+ * windows[g] is the sum of the listed members' windows; a member listed twice
+ * counts twice.
+ *  All sets must share window, mask, elem_words, policy kind, hash flavour and
+ *  nonce (else SKS_E_ARG naming "window", "mask", "policy kind", "flavour" or
+ *  "nonce").
+ *  SKS_FRAC_MOD: and policy.param ("policy param").
+ *  SKS_BOTTOM_S: sets of different s are allowed; the result's param is the
+ *    smallest, and every sketch keeps its min(param, distinct elements) smallest
+ *    by (frac_min_hash, k-mer value), the rule of sks_sketch_set_downsample.
+ * The result carries the common window, mask, flavour and nonce and has no
+ * names (sks_sketch_set_set_names).  The source sets are not modified.
+ * SKS_E_ARG, decided on the host before anything is launched: a null ctx, sets,
+ * out or set (before any device is touched), n_sets == 0, a null group_off or
+ * members where entries are needed, a group_off that decreases or does not
+ * start at 0, a member index >= the number of source sketches (the message
+ * names the index), a set on another device than the context's.  A group whose
+ * members' sizes sum to 2^32 or more is SKS_E_UNSUPPORTED.  *out is NULL on
+ * every failure.
+ * Waits for the context's stream once, to read the new sizes back, and once
+ * more when a bottom-s sketch has to be cut; the elements are then written by a
+ * kernel queued on that stream (sks_ctx_synchronize waits for it; the source
+ * sets may be freed with sks_sketch_set_free at once). */
+int sks_sketch_set_merge(sks_ctx* ctx, const sks_sketch_set* const* sets, uint32_t n_sets,
+                         const uint32_t* group_off, const uint32_t* members, uint32_t n_groups,
+                         sks_sketch_set** out);
 
 /* ---- ordered k-mer lists: nucleotide_string_list_to_kmers (kmer_sliding.cpp:112-238) ---
  * Every selected window of every segment, in stream order, duplicates kept —

@@ -13,11 +13,19 @@
 //       a coarser copy of a database (sks_sketch_set_downsample): FracMinHash 1/c
 //       with c a multiple of the database's, or bottom-s with a smaller s; the
 //       result equals a database indexed at c directly, names kept
+//   sks-search merge <out.sks> <groups.tsv> <in.sks> [<in.sks> ...]
+//       one sketch per group, the union of the sketches the group lists
+//       (sks_sketch_set_merge): groups.tsv holds lines group_name<TAB>sketch_name,
+//       the sketches are found by name across the input databases, the groups
+//       come in order of first appearance and name the output's sketches; the
+//       result equals a database indexed from each group's sequences together
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -66,8 +74,9 @@ int usage(const char* argv0) {
   std::fprintf(stderr,
                "usage: %s index <out.sks> <w> <k> <c> <fasta files...>\n"
                "       %s query <db.sks> <min_containment> <out.csv> <fasta files...>\n"
-               "       %s downsample <in.sks> <c> <out.sks>\n",
-               argv0, argv0, argv0);
+               "       %s downsample <in.sks> <c> <out.sks>\n"
+               "       %s merge <out.sks> <groups.tsv> <in.sks> [<in.sks> ...]\n",
+               argv0, argv0, argv0, argv0);
   return 64;
 }
 
@@ -140,6 +149,65 @@ int run(int argc, char* argv[]) {
     std::printf("%u sketches -> %s\n", sks_sketch_set_num(small), argv[4]);
     sks_sketch_set_free(small);
     sks_sketch_set_free(db);
+    sks_ctx_destroy(ctx);
+    return 0;
+  }
+  if (mode == "merge" && argc >= 5) {
+    check(sks_ctx_create(0, nullptr, &ctx));
+    // every input sketch by name, numbered as the library numbers the sources
+    std::vector<sks_sketch_set*> dbs;
+    std::map<std::string, uint32_t> index_of;
+    uint32_t n_src = 0;
+    for (int i = 4; i < argc; ++i) {
+      sks_sketch_set* db = nullptr;
+      check(sks_sketch_set_load(ctx, argv[i], &db));
+      dbs.push_back(db);
+      const uint32_t n = sks_sketch_set_num(db);
+      for (uint32_t k = 0; k < n; ++k) {
+        const char* name = sks_sketch_set_name(db, k);
+        if (!name) throw std::runtime_error(std::string(argv[i]) + " has no sketch names");
+        if (!index_of.emplace(name, n_src + k).second)
+          throw std::runtime_error(std::string("sketch name found twice in the inputs: ") + name);
+      }
+      n_src += n;
+    }
+    std::ifstream tsv(argv[3]);
+    if (!tsv) throw std::runtime_error(std::string("cannot read ") + argv[3]);
+    std::vector<std::string> group_names;
+    std::map<std::string, size_t> group_of;
+    std::vector<std::vector<uint32_t>> listed;
+    std::string line;
+    while (std::getline(tsv, line)) {
+      if (!line.empty() && line.back() == '\r') line.pop_back();
+      if (line.empty()) continue;
+      const size_t tab = line.find('\t');
+      if (tab == std::string::npos) throw std::runtime_error("groups line without a tab: " + line);
+      const std::string group = line.substr(0, tab), sketch = line.substr(tab + 1);
+      const auto src = index_of.find(sketch);
+      if (src == index_of.end()) throw std::runtime_error("sketch name not found in the inputs: " + sketch);
+      const auto g = group_of.emplace(group, group_names.size());
+      if (g.second) {
+        group_names.push_back(group);
+        listed.emplace_back();
+      }
+      listed[g.first->second].push_back(src->second);
+    }
+    std::vector<uint32_t> group_off{0}, members;
+    for (const auto& l : listed) {
+      members.insert(members.end(), l.begin(), l.end());
+      group_off.push_back((uint32_t)members.size());
+    }
+    sks_sketch_set* merged = nullptr;
+    check(sks_sketch_set_merge(ctx, dbs.data(), (uint32_t)dbs.size(), group_off.data(), members.data(),
+                               (uint32_t)listed.size(), &merged));
+    check(sks_ctx_synchronize(ctx));
+    std::vector<const char*> names;
+    for (const std::string& g : group_names) names.push_back(g.c_str());
+    check(sks_sketch_set_set_names(merged, names.data()));
+    check(sks_sketch_set_save(merged, argv[2]));
+    std::printf("%u sketches -> %s\n", sks_sketch_set_num(merged), argv[2]);
+    sks_sketch_set_free(merged);
+    for (sks_sketch_set* db : dbs) sks_sketch_set_free(db);
     sks_ctx_destroy(ctx);
     return 0;
   }

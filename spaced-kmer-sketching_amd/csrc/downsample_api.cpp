@@ -1,6 +1,8 @@
 // C-ABI implementation (include/sks.h): sks_sketch_set_downsample — a coarser
 // copy of a device sketch set (FracMinHash 1/c -> 1/c', bottom-s -> bottom-s')
 // made from the set's own elements by the filter kernels of downsample.hip.
+// downsample_arrays, the work after the argument checks, also cuts the bottom-s
+// sketches of sks_sketch_set_merge (merge_api.cpp).
 #include <numeric>
 
 #include "sks_ctx.hpp"
@@ -8,42 +10,21 @@
 
 using namespace sks;
 
-extern "C" int sks_sketch_set_downsample(sks_ctx* c, const sks_sketch_set* src, uint64_t param,
-                                         sks_sketch_set** out) {
-  if (out) *out = nullptr;
-  if (!c || !src || !out) return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: null argument");
-  if (param == 0) return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: policy param must be > 0");
-  if (src->device != c->device)
-    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: the set is on device " + std::to_string(src->device) +
-                                    ", the context on device " + std::to_string(c->device));
-  const sks_policy& pol = src->policy;
+int sks::downsample_arrays(sks_ctx* c, const char* who, const uint64_t* d_data, const uint64_t* d_starts,
+                           const uint32_t* d_sizes, const std::vector<uint32_t>& src_sizes, const sks_sketch_set& like,
+                           uint64_t param, SetPtr* out) {
+  const sks_policy& pol = like.policy;
   const bool bottom = pol.kind == SKS_BOTTOM_S;
-  if (!bottom && pol.kind != SKS_FRAC_MOD)
-    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: unknown policy kind");
-  if (pol.flavour != 0 && pol.flavour != 1)
-    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: unknown hash flavour");
-  if (src->elem_words != 1 && src->elem_words != 2)
-    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: elements of 1 or 2 words only");
-  if (!bottom && (pol.param == 0 || param % pol.param != 0))
-    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: policy param " + std::to_string(param) +
-                                    " is not a multiple of the set's " + std::to_string(pol.param) +
-                                    " (a FracMinHash sketch can only be made coarser)");
-  if (bottom && param > pol.param)
-    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: policy param " + std::to_string(param) +
-                                    " is larger than the set's " + std::to_string(pol.param) +
-                                    " (a bottom-s sketch can only be made smaller)");
-
-  DeviceGuard guard(c->device);
   hipStream_t st = c->stream;
-  const uint32_t n = src->n;
-  const int ew = src->elem_words;
+  const uint32_t n = (uint32_t)src_sizes.size();
+  const int ew = like.elem_words;
 
   // chunks and elements before each sketch
   std::vector<uint64_t> chunk_off(n + 1, 0), dense_off(n + 1, 0);
   uint64_t max_len = 0;
   bool selects = false;  // bottom-s: a sketch holds more than `param` elements
   for (uint32_t g = 0; g < n; ++g) {
-    const uint64_t sz = src->sizes[g];
+    const uint64_t sz = src_sizes[g];
     chunk_off[g + 1] = chunk_off[g] + (sz + kDownsampleChunk - 1) / kDownsampleChunk;
     dense_off[g + 1] = dense_off[g] + sz;
     max_len = std::max(max_len, sz);
@@ -57,8 +38,8 @@ extern "C" int sks_sketch_set_downsample(sks_ctx* c, const sks_sketch_set* src, 
   sks_policy coarser = pol;
   coarser.param = param;
   SetPtr set;
-  SKS_TRY(make_sketch_set(c->device, ew, src->window, src->mask, coarser, std::vector<uint32_t>(n, 0), src->windows,
-                          src->names, nullptr, st, MetaUpload::kNone, &set));
+  SKS_TRY(make_sketch_set(c->device, ew, like.window, like.mask, coarser, std::vector<uint32_t>(n, 0), like.windows,
+                          like.names, nullptr, st, MetaUpload::kNone, &set));
 
   MetaArena arena(c);
   const size_t o_chunk = arena.add(chunk_off), o_dense = arena.add(dense_off);
@@ -69,12 +50,12 @@ extern "C" int sks_sketch_set_downsample(sks_ctx* c, const sks_sketch_set* src, 
   uint64_t* d_offs = reinterpret_cast<uint64_t*>(c->pos.ptr);
 
   DownsampleArgs a{};
-  a.data = src->d_data();
-  a.starts = src->d_starts();
-  a.sizes = src->d_sizes();
+  a.data = d_data;
+  a.starts = d_starts;
+  a.sizes = d_sizes;
   a.chunk_off = arena.ptr(o_chunk);
   a.dense_off = arena.ptr(o_dense);
-  a.kconst = sks::fmh_const(src->mask[0], src->mask[1], src->window, pol.nonce, pol.flavour);
+  a.kconst = sks::fmh_const(like.mask[0], like.mask[1], like.window, pol.nonce, pol.flavour);
   if (mode == kDownsampleFrac) {
     const sks::DivTest dt = sks::make_div_test(param);
     a.low_mask = dt.low_mask;
@@ -104,14 +85,47 @@ extern "C" int sks_sketch_set_downsample(sks_ctx* c, const sks_sketch_set* src, 
   SKS_HIP(sks::pinned_d2h(sizes.data(), set->d_sizes(), n * sizeof(uint32_t), st));
   uint64_t total = 0;
   for (uint32_t g = 0; g < n; ++g) {
-    if (sizes[g] > src->sizes[g])
-      return sks::fail(SKS_E_HIP, "sks_sketch_set_downsample: a filtered sketch is larger than its source");
+    if (sizes[g] > src_sizes[g])
+      return sks::fail(SKS_E_HIP, std::string(who) + ": a filtered sketch is larger than its source");
     set->starts[g] = total;
     total += sizes[g];
   }
   SKS_TRY(alloc_u64(set->data, total * ew, st));
   set->sizes = sizes;
   SKS_HIP(sks::downsample_scatter(a, ew, pol.flavour, mode, n, max_len, d_offs, set->d_data(), st));
+  *out = std::move(set);
+  return SKS_OK;
+}
+
+extern "C" int sks_sketch_set_downsample(sks_ctx* c, const sks_sketch_set* src, uint64_t param,
+                                         sks_sketch_set** out) {
+  if (out) *out = nullptr;
+  if (!c || !src || !out) return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: null argument");
+  if (param == 0) return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: policy param must be > 0");
+  if (src->device != c->device)
+    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: the set is on device " + std::to_string(src->device) +
+                                    ", the context on device " + std::to_string(c->device));
+  const sks_policy& pol = src->policy;
+  const bool bottom = pol.kind == SKS_BOTTOM_S;
+  if (!bottom && pol.kind != SKS_FRAC_MOD)
+    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: unknown policy kind");
+  if (pol.flavour != 0 && pol.flavour != 1)
+    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: unknown hash flavour");
+  if (src->elem_words != 1 && src->elem_words != 2)
+    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: elements of 1 or 2 words only");
+  if (!bottom && (pol.param == 0 || param % pol.param != 0))
+    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: policy param " + std::to_string(param) +
+                                    " is not a multiple of the set's " + std::to_string(pol.param) +
+                                    " (a FracMinHash sketch can only be made coarser)");
+  if (bottom && param > pol.param)
+    return sks::fail(SKS_E_ARG, "sks_sketch_set_downsample: policy param " + std::to_string(param) +
+                                    " is larger than the set's " + std::to_string(pol.param) +
+                                    " (a bottom-s sketch can only be made smaller)");
+
+  DeviceGuard guard(c->device);
+  SetPtr set;
+  SKS_TRY(downsample_arrays(c, "sks_sketch_set_downsample", src->d_data(), src->d_starts(), src->d_sizes(), src->sizes,
+                            *src, param, &set));
   *out = set.release();
   return SKS_OK;
 }

@@ -1,6 +1,6 @@
 // What the C-ABI translation units that run on a device share (ctx.cpp,
 // host_mem.cpp, sketch_set.cpp, kmer_list.cpp, build.cpp, build_post.cpp,
-// pairs.cpp, search_api.cpp, downsample_api.cpp): the context, the sketch set
+// pairs.cpp, search_api.cpp, downsample_api.cpp, merge_api.cpp): the context, the sketch set
 // and k-mer list with the device blocks they own, the error macros, the
 // metadata arena and small argument helpers.
 #pragma once
@@ -20,6 +20,7 @@
 #include "ingress.hpp"
 #include "intersect.hpp"
 #include "join.hpp"
+#include "merge.hpp"
 #include "post.hpp"
 #include "scan.hpp"
 #include "scratch_carve.hpp"
@@ -191,6 +192,15 @@ enum class MetaUpload { kNone, kStream, kBlocking };
 int make_sketch_set(int device, int elem_words, int window, const uint64_t mask[2], const sks_policy& policy,
                     std::vector<uint32_t> sizes, std::vector<uint64_t> windows, std::vector<std::string> names,
                     const uint64_t* data_words, hipStream_t st, MetaUpload up, SetPtr* out);
+
+// ---- filters over a set's arrays (downsample_api.cpp) -----------------------------------
+// sks_sketch_set_downsample after its argument checks, over the CSR arrays
+// (d_data, d_starts, d_sizes; src_sizes on the host) of sketches made as `like`
+// says (elem_words, window, mask, policy; its windows and names are carried
+// over): a new set at policy param `param`.  Waits for the stream once.
+int downsample_arrays(sks_ctx* c, const char* who, const uint64_t* d_data, const uint64_t* d_starts,
+                      const uint32_t* d_sizes, const std::vector<uint32_t>& src_sizes, const sks_sketch_set& like,
+                      uint64_t param, SetPtr* out);
 
 // ---- argument helpers (ctx.cpp) ---------------------------------------------------------
 // The opening checks of the entry points that take a join layout: a context, a

@@ -75,6 +75,7 @@ EXPORTED = [
     "sks_join_layout_bounds_for_mask", "sks_layout_tiles_ani",
     "sks_ctx_set_frac_post", "sks_ctx_last_build_path",
     "sks_search", "sks_search_sets", "sks_ctx_set_search_batch", "sks_sketch_set_downsample",
+    "sks_sketch_set_merge",
 ]
 
 # sks_hit (include/sks.h): one record of Context.search's result
@@ -183,6 +184,7 @@ def lib():
     L.sks_sketch_set_load.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
     L.sks_sketch_set_concat.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
     L.sks_sketch_set_downsample.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp)]
+    L.sks_sketch_set_merge.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(vp)]
     L.sks_kmer_list_build.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, u64p,
                                       C.POINTER(Policy), C.POINTER(vp)]
     L.sks_windows_dense.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, u64p, vp, vp]
@@ -634,6 +636,19 @@ class Context:
         build at `param` (FracMinHash: a multiple of the set's c; bottom-s: s' <= s)."""
         h = C.c_void_p()
         check(lib().sks_sketch_set_downsample(self.h, sketch_set.h, int(param), C.byref(h)))
+        return SketchSet(h)
+
+    def merge(self, sets, groups):
+        """sks_sketch_set_merge: one sketch per entry of `groups`, the union of the
+        source sketches it lists (indices into the sketches of `sets` in concat
+        order: set 0's, then set 1's, ...).  The result has no names."""
+        arr = (C.c_void_p * len(sets))(*[s.h for s in sets])
+        off = np.zeros(len(groups) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(g) for g in groups], dtype=np.int64)
+        mem = np.array([i for g in groups for i in g] + [0], dtype=np.uint32)
+        h = C.c_void_p()
+        check(lib().sks_sketch_set_merge(self.h, arr, len(sets), off.ctypes.data, mem.ctypes.data, len(groups),
+                                         C.byref(h)))
         return SketchSet(h)
 
     def intersect_pairs(self, data_ptr, starts_ptr, sizes_ptr, elem_words, a_ptr, b_ptr,
