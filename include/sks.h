@@ -26,7 +26,8 @@ extern "C" {
                               the buckets per region, which the join reads: layouts built by
                               an ABI-2 library (rows without that word) must not be joined by
                               this one (round 5); later additions within 3 (new symbols
-                              only): sks_sketch_set_downsample, sks_sketch_set_merge.  2: deduplicated join layout (masks, region
+                              only): sks_sketch_set_downsample, sks_sketch_set_merge, sks_cluster,
+                              sks_cluster_set.  2: deduplicated join layout (masks, region
                               ends), elem_words on the layout entry points,
                               sks_ctx_set_join_check; later additions within 2 (new symbols
                               only): sks_ani_rows, sks_intersect_layout_ani, sks_host_alloc,
@@ -541,6 +542,51 @@ int sks_search_sets(sks_ctx* ctx, const sks_sketch_set* queries, const sks_sketc
 /* Diagnostics: 64-sketch reference blocks per batch of sks_search (0, the
  * default: the engine's choice, which keeps a batch's count tiles within 256 MiB). */
 int sks_ctx_set_search_batch(sks_ctx* ctx, uint32_t ref_blocks);
+
+/* ---- single-linkage clusters (no reference equivalent) ---------------------------------
+ * "Which of these sketches are the same thing?": the connected components of the
+ * graph that links two sketches i != j of one set iff, with shared = |S_i ∩ S_j|,
+ *   shared >= max(min_shared, 1)  and
+ *   max(containment(shared, |S_i|), containment(shared, |S_j|)) >= min_containment
+ * (containment as everywhere else: a double division), which is to say iff
+ * sks_search_sets(set, set, min_containment, min_shared) reports (i, j) or
+ * (j, i).  An empty sketch shares nothing and is a cluster of its own;
+ * min_containment <= 0 links every pair sharing max(min_shared, 1) k-mers; a
+ * min_containment no pair can meet gives n clusters of one.
+ * The result is canonical, whatever the order in which links are found:
+ * clusters are numbered 0 .. C-1 by ascending smallest member, so sketch 0 is in
+ * cluster 0.  d_cluster[i] (device, n x u32) is the cluster of sketch i;
+ * d_rep[c] (device, room for n x u32, C written) the representative of cluster
+ * c, its member with the most elements, ties to the smallest index; either may
+ * be NULL.  *n_clusters (host) receives C.
+ * The set's join layout is built once (context scratch) and joined with itself,
+ * the tiles on or above the diagonal only, in batches of whole columns of
+ * 64-sketch blocks (sks_ctx_set_search_batch; by default a batch's count tiles
+ * stay within 256 MiB); a kernel turns each batch's tiles into unions in a
+ * parent array.  Scratch depends on n and on one batch, never on the number of
+ * linked pairs, and only the labels leave the device.
+ * Device-array form: the set as in the intersection entry points, with the
+ * largest sketch (max_size) and the sizes' sum (total, or an upper bound); group
+ * bounds are sampled from the set.  kmer_num_ones is taken for symmetry with
+ * sks_search only: the rule is on containment.  Checked on the host, leaving
+ * *n_clusters = 0: null ctx (before any device is touched), null n_clusters,
+ * NaN min_containment, elem_words not 1 or 2, kmer_num_ones <= 0 -> SKS_E_ARG;
+ * total >= 2^32 -> SKS_E_UNSUPPORTED; n == 0 -> SKS_OK and 0 clusters.  A layout
+ * the build could not place (adversarial 128-bit values) -> SKS_E_UNSUPPORTED
+ * ("invalid layout"), 0 clusters: nothing is linked from such a layout.
+ * The call waits for the stream once, to read C back; the labels and
+ * representatives are written by kernels queued before that wait.
+ * sks_ctx_last_intersect_ms then times the whole call. */
+int sks_cluster(sks_ctx* ctx, const uint64_t* d_data, const uint64_t* d_starts, const uint32_t* d_sizes,
+                uint32_t n, uint32_t max_size, uint64_t total, int elem_words, int kmer_num_ones,
+                double min_containment, int32_t min_shared, uint32_t* d_cluster, uint32_t* d_rep,
+                uint32_t* n_clusters);
+/* The same for a sketch set (null set, or a set on another device than the
+ * context -> SKS_E_ARG).  The group bounds are the mask-derived ones
+ * (sks_join_layout_bounds_for_mask); if the layout cannot be placed with them,
+ * the call runs once more with bounds sampled from the set before giving up. */
+int sks_cluster_set(sks_ctx* ctx, const sks_sketch_set* set, double min_containment, int32_t min_shared,
+                    uint32_t* d_cluster, uint32_t* d_rep, uint32_t* n_clusters);
 
 /* Pinned host memory the device reads and writes directly (mapped into every
  * device's address space): the destination of a fused ANI matrix.  coherent:

@@ -19,6 +19,15 @@
 //       the sketches are found by name across the input databases, the groups
 //       come in order of first appearance and name the output's sketches; the
 //       result equals a database indexed from each group's sequences together
+//   sks-search cluster <db.sks> <min_containment> <out.tsv> [<reps.sks>]
+//       single-linkage clusters of the database (sks_cluster_set, min_shared 1):
+//       two sketches are linked when the larger of their two containments is at
+//       least min_containment.  One line per sketch, in database order:
+//         cluster<TAB>representative name<TAB>sketch name
+//       (clusters numbered by their first member; a cluster's representative is
+//       its largest sketch; names fall back to the index).  With reps.sks the
+//       representatives are written as a database, in cluster order, each with
+//       its elements, windows and name (dereplication)
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -75,8 +84,9 @@ int usage(const char* argv0) {
                "usage: %s index <out.sks> <w> <k> <c> <fasta files...>\n"
                "       %s query <db.sks> <min_containment> <out.csv> <fasta files...>\n"
                "       %s downsample <in.sks> <c> <out.sks>\n"
-               "       %s merge <out.sks> <groups.tsv> <in.sks> [<in.sks> ...]\n",
-               argv0, argv0, argv0, argv0);
+               "       %s merge <out.sks> <groups.tsv> <in.sks> [<in.sks> ...]\n"
+               "       %s cluster <db.sks> <min_containment> <out.tsv> [<reps.sks>]\n",
+               argv0, argv0, argv0, argv0, argv0);
   return 64;
 }
 
@@ -208,6 +218,59 @@ int run(int argc, char* argv[]) {
     std::printf("%u sketches -> %s\n", sks_sketch_set_num(merged), argv[2]);
     sks_sketch_set_free(merged);
     for (sks_sketch_set* db : dbs) sks_sketch_set_free(db);
+    sks_ctx_destroy(ctx);
+    return 0;
+  }
+  if (mode == "cluster" && (argc == 5 || argc == 6)) {
+    char* end = nullptr;
+    const double min_containment = std::strtod(argv[3], &end);
+    if (end == argv[3] || *end) throw std::runtime_error(std::string("bad min_containment: ") + argv[3]);
+    check(sks_ctx_create(0, nullptr, &ctx));
+    sks_sketch_set* db = nullptr;
+    check(sks_sketch_set_load(ctx, argv[2], &db));
+    const uint32_t n = sks_sketch_set_num(db);
+    std::vector<uint32_t> label(n), rep(n);
+    uint32_t n_clusters = 0;
+    if (n) {
+      void* d_out = nullptr;  // labels, then representatives
+      check_hip(hipMalloc(&d_out, (size_t)n * 2 * sizeof(uint32_t)), "hipMalloc");
+      uint32_t* d_label = static_cast<uint32_t*>(d_out);
+      const int rc = sks_cluster_set(ctx, db, min_containment, 1, d_label, d_label + n, &n_clusters);
+      if (rc == SKS_OK && sks_ctx_synchronize(ctx) == SKS_OK) {
+        check_hip(hipMemcpy(label.data(), d_label, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy");
+        check_hip(hipMemcpy(rep.data(), d_label + n, (size_t)n_clusters * sizeof(uint32_t), hipMemcpyDeviceToHost),
+                  "hipMemcpy");
+      }
+      (void)hipFree(d_out);
+      check(rc);
+    }
+    rep.resize(n_clusters);
+    const auto name_of = [db](uint32_t i) {
+      const char* name = sks_sketch_set_name(db, i);
+      return name ? std::string(name) : std::to_string(i);
+    };
+    FILE* out = std::fopen(argv[4], "w");
+    if (!out) throw std::runtime_error(std::string("cannot write ") + argv[4]);
+    for (uint32_t i = 0; i < n; ++i)
+      std::fprintf(out, "%u\t%s\t%s\n", label[i], name_of(rep[label[i]]).c_str(), name_of(i).c_str());
+    std::fclose(out);
+    if (argc == 6) {
+      // the representatives as a database: one single-member group each
+      std::vector<uint32_t> group_off(n_clusters + 1);
+      for (uint32_t g = 0; g <= n_clusters; ++g) group_off[g] = g;
+      sks_sketch_set* reps = nullptr;
+      check(sks_sketch_set_merge(ctx, &db, 1, group_off.data(), rep.data(), n_clusters, &reps));
+      check(sks_ctx_synchronize(ctx));
+      std::vector<std::string> rep_names;
+      for (uint32_t r : rep) rep_names.push_back(name_of(r));
+      std::vector<const char*> names;
+      for (const std::string& r : rep_names) names.push_back(r.c_str());
+      if (n_clusters) check(sks_sketch_set_set_names(reps, names.data()));
+      check(sks_sketch_set_save(reps, argv[5]));
+      sks_sketch_set_free(reps);
+    }
+    std::printf("%u sketches, %u clusters -> %s\n", n, n_clusters, argv[4]);
+    sks_sketch_set_free(db);
     sks_ctx_destroy(ctx);
     return 0;
   }

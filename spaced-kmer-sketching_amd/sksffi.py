@@ -75,7 +75,7 @@ EXPORTED = [
     "sks_join_layout_bounds_for_mask", "sks_layout_tiles_ani",
     "sks_ctx_set_frac_post", "sks_ctx_last_build_path",
     "sks_search", "sks_search_sets", "sks_ctx_set_search_batch", "sks_sketch_set_downsample",
-    "sks_sketch_set_merge",
+    "sks_sketch_set_merge", "sks_cluster", "sks_cluster_set",
 ]
 
 # sks_hit (include/sks.h): one record of Context.search's result
@@ -230,6 +230,9 @@ def lib():
                              u64p]
     L.sks_search_sets.argtypes = [vp, vp, vp, C.c_double, C.c_int32, vp, C.c_uint64, u64p]
     L.sks_ctx_set_search_batch.argtypes = [vp, C.c_uint32]
+    L.sks_cluster.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_double,
+                              C.c_int32, vp, vp, C.POINTER(C.c_uint32)]
+    L.sks_cluster_set.argtypes = [vp, vp, C.c_double, C.c_int32, vp, vp, C.POINTER(C.c_uint32)]
     _lib = L
     return L
 
@@ -720,6 +723,50 @@ class Context:
                                     C.c_void_p(buf.data_ptr()), cap, C.byref(n)))
         self.synchronize()
         return buf.cpu().numpy().view(HIT_DTYPE)[:int(n.value)].copy()
+
+    def cluster_set_raw(self, sketch_set, min_containment, min_shared, d_cluster, d_rep):
+        """sks_cluster_set with caller buffers (device pointers, 0 for NULL; the set
+        may be None); returns (status code, number of clusters) without raising."""
+        n = C.c_uint32(0xffffffff)
+        rc = lib().sks_cluster_set(self.h, sketch_set.h if sketch_set is not None else None, float(min_containment),
+                                   int(min_shared), C.c_void_p(d_cluster) if d_cluster else None,
+                                   C.c_void_p(d_rep) if d_rep else None, C.byref(n))
+        return rc, int(n.value)
+
+    def cluster_arrays_raw(self, side, elem_words, kmer_num_ones, min_containment, min_shared, d_cluster, d_rep):
+        """sks_cluster with caller buffers; `side` as search_arrays takes it.
+        Returns (status code, number of clusters) without raising."""
+        v = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        n = C.c_uint32(0xffffffff)
+        rc = lib().sks_cluster(self.h, v(side[0]), v(side[1]), v(side[2]), int(side[3]), int(side[4]), int(side[5]),
+                               int(elem_words), int(kmer_num_ones), float(min_containment), int(min_shared),
+                               v(d_cluster), v(d_rep), C.byref(n))
+        return rc, int(n.value)
+
+    def _cluster(self, n, call):
+        import torch
+        dev = torch.device("cuda", self.device)
+        labels = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        reps = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        rc, c = call(labels.data_ptr(), reps.data_ptr())
+        check(rc)
+        self.synchronize()
+        return (labels.cpu().numpy().view(np.uint32)[:n].copy(), reps.cpu().numpy().view(np.uint32)[:c].copy())
+
+    def cluster(self, sketch_set, min_containment=0.0, min_shared=1):
+        """sks_cluster_set: single-linkage clusters of a SketchSet.  Two sketches are
+        linked iff they share at least max(min_shared, 1) k-mers and the larger of
+        their two containments is >= min_containment.  Returns (labels u32[n],
+        reps u32[C]): clusters numbered by ascending smallest member, each
+        cluster's representative its largest sketch (ties: the smallest index)."""
+        return self._cluster(sketch_set.n, lambda lab, rep: self.cluster_set_raw(sketch_set, min_containment,
+                                                                                 min_shared, lab, rep))
+
+    def cluster_arrays(self, side, elem_words, kmer_num_ones, min_containment=0.0, min_shared=1):
+        """sks_cluster, the device-array form: side is (data, starts, sizes, n,
+        max_size, total) with device pointers, as search_arrays takes a side."""
+        return self._cluster(int(side[3]), lambda lab, rep: self.cluster_arrays_raw(
+            side, elem_words, kmer_num_ones, min_containment, min_shared, lab, rep))
 
     def synth_bases(self, d_out_ptr, n, seed, mut_seed=0, mut_rate=0.0, pos_offset=0):
         check(lib().sks_synth_bases(self.h, C.c_void_p(d_out_ptr), n, seed, mut_seed, mut_rate,
