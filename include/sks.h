@@ -27,7 +27,8 @@ extern "C" {
                               an ABI-2 library (rows without that word) must not be joined by
                               this one (round 5); later additions within 3 (new symbols
                               only): sks_sketch_set_downsample, sks_sketch_set_merge, sks_cluster,
-                              sks_cluster_set.  2: deduplicated join layout (masks, region
+                              sks_cluster_set, sks_gather, sks_gather_sets,
+                              sks_ctx_set_gather_rounds.  2: deduplicated join layout (masks, region
                               ends), elem_words on the layout entry points,
                               sks_ctx_set_join_check; later additions within 2 (new symbols
                               only): sks_ani_rows, sks_intersect_layout_ani, sks_host_alloc,
@@ -587,6 +588,63 @@ int sks_cluster(sks_ctx* ctx, const uint64_t* d_data, const uint64_t* d_starts, 
  * the call runs once more with bounds sampled from the set before giving up. */
 int sks_cluster_set(sks_ctx* ctx, const sks_sketch_set* set, double min_containment, int32_t min_shared,
                     uint32_t* d_cluster, uint32_t* d_rep, uint32_t* n_clusters);
+
+/* ---- gather: greedy min-set cover of a query (no reference equivalent) ------------------
+ * "This sample is a mixture: which references does it contain, each counted only
+ * for what the earlier ones did not explain?"  Q is one query sketch, R_0 ..
+ * R_{n-1} reference sketches over the same k-mer space (ascending, unique
+ * elements; with elem_words 2 ordered by the 128-bit value, hi first).  With
+ * thr = max(min_shared, 1) and Q_rem = Q, every round computes
+ * new_r = |Q_rem ∩ R_r| for every r and picks the r with the largest new_r, ties
+ * to the smallest index.  If that new_r < thr, or max_rounds rounds have been
+ * reported (0: no limit), the call stops; otherwise r is reported and
+ * Q_rem <- Q_rem \ R_r.  Hits come out in round order; no reference is reported
+ * twice.  Every value is an integer or one double division of integers, so the
+ * result is exact and deterministic.
+ * Near-identical references all pass a containment threshold of sks_search;
+ * gather reports one of them and the rest drop out, nothing of theirs being
+ * left to explain.
+ * The call finds, once, the position in Q of every reference element (scratch
+ * of O(q_size + r_total) words on the context), then runs the rounds on the
+ * device over a bitmap of Q's unexplained elements, queued in groups
+ * (sks_ctx_set_gather_rounds) with one host wait per group and one after the
+ * membership pass.  sks_ctx_last_intersect_ms then times the whole call. */
+typedef struct sks_gather_hit {  /* 32 bytes */
+  uint32_t ref;         /* index into the references                                          */
+  int32_t  shared;      /* |Q ∩ R_ref|, with the whole query                                  */
+  int32_t  shared_new;  /* |Q_rem ∩ R_ref| when chosen: the elements this round explains       */
+  int32_t  ref_size;    /* |R_ref|                                                            */
+  double   f_query_new; /* containment(shared_new, |Q|)                                       */
+  double   ani;         /* binomial_estimator(containment(shared, ref_size), kmer_num_ones)   */
+} sks_gather_hit;
+/* Device-array form: the query's q_size elements at d_q (device), the references
+ * as in sks_search (r_max_size is taken for symmetry with it; r_total is the
+ * sizes' sum or an upper bound; sizes adding up to more -> SKS_E_ARG).
+ * *n_hits (host) always receives the exact number of rounds, *n_unexplained
+ * (host, may be NULL) |Q_rem| at the end.  d_hits (device, hit_cap records) may be
+ * NULL: a size query.  *n_hits > hit_cap -> SKS_E_LENGTH, the contents of d_hits
+ * then unspecified.  min(r_n, q_size) records always suffice.
+ * Checked on the host, leaving *n_hits = 0: null ctx (before any device is
+ * touched), null n_hits, elem_words not 1 or 2, kmer_num_ones <= 0, null arrays
+ * where entries are needed -> SKS_E_ARG; r_total >= 2^32 (or 2^31 query elements
+ * or references) -> SKS_E_UNSUPPORTED; q_size == 0 or r_n == 0 -> SKS_OK, 0 hits. */
+int sks_gather(sks_ctx* ctx, const uint64_t* d_q, uint32_t q_size, const uint64_t* d_r_data,
+               const uint64_t* d_r_starts, const uint32_t* d_r_sizes, uint32_t r_n, uint32_t r_max_size,
+               uint64_t r_total, int elem_words, int kmer_num_ones, int32_t min_shared, uint32_t max_rounds,
+               sks_gather_hit* d_hits, uint64_t hit_cap, uint64_t* n_hits, uint32_t* n_unexplained);
+/* The same for sketch `q` of `queries` (q >= its number -> SKS_E_ARG) against the
+ * set `refs`.  Both sets must share window, mask, elem_words, policy kind, hash
+ * flavour, nonce and policy param (the checks and messages of sks_search_sets),
+ * and both must be SKS_FRAC_MOD: a bottom-s set is SKS_E_ARG naming "policy
+ * kind", because subtraction only means something when every sketch samples the
+ * same hash space.  Both sets must live on the context's device.
+ * kmer_num_ones = popcount(mask) / 2. */
+int sks_gather_sets(sks_ctx* ctx, const sks_sketch_set* queries, uint32_t q, const sks_sketch_set* refs,
+                    int32_t min_shared, uint32_t max_rounds, sks_gather_hit* d_hits, uint64_t hit_cap,
+                    uint64_t* n_hits, uint32_t* n_unexplained);
+/* Diagnostics: rounds of sks_gather queued per host wait (0, the default: the
+ * engine's choice, gather_plan.hpp). */
+int sks_ctx_set_gather_rounds(sks_ctx* ctx, uint32_t rounds_per_wait);
 
 /* Pinned host memory the device reads and writes directly (mapped into every
  * device's address space): the destination of a fused ANI matrix.  coherent:

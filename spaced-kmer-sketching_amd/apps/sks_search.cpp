@@ -28,7 +28,16 @@
 //       its largest sketch; names fall back to the index).  With reps.sks the
 //       representatives are written as a database, in cluster order, each with
 //       its elements, windows and name (dereplication)
+//   sks-search gather <db.sks> <min_shared> <out.csv> <q.fa> ...
+//       each FASTA file is one query (a mixture), sketched with the database's
+//       window, mask and policy; the greedy min-set cover of it by the database
+//       (sks_gather_sets): per round the reference explaining the most still
+//       unexplained query k-mers, at least min_shared of them:
+//         Query,Round,Reference,Shared,SharedNew,RefSize,FQueryNew,ANI   (doubles as %.17g)
+//       and after each query's rows one line  Query,-,unexplained,<n_unexplained>,,,,
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include <cstdio>
 #include <cstdlib>
@@ -85,8 +94,9 @@ int usage(const char* argv0) {
                "       %s query <db.sks> <min_containment> <out.csv> <fasta files...>\n"
                "       %s downsample <in.sks> <c> <out.sks>\n"
                "       %s merge <out.sks> <groups.tsv> <in.sks> [<in.sks> ...]\n"
-               "       %s cluster <db.sks> <min_containment> <out.tsv> [<reps.sks>]\n",
-               argv0, argv0, argv0, argv0, argv0);
+               "       %s cluster <db.sks> <min_containment> <out.tsv> [<reps.sks>]\n"
+               "       %s gather <db.sks> <min_shared> <out.csv> <fasta files...>\n",
+               argv0, argv0, argv0, argv0, argv0, argv0);
   return 64;
 }
 
@@ -270,6 +280,54 @@ int run(int argc, char* argv[]) {
       sks_sketch_set_free(reps);
     }
     std::printf("%u sketches, %u clusters -> %s\n", n, n_clusters, argv[4]);
+    sks_sketch_set_free(db);
+    sks_ctx_destroy(ctx);
+    return 0;
+  }
+  if (mode == "gather" && argc >= 6) {
+    char* end = nullptr;
+    const long min_shared = std::strtol(argv[3], &end, 10);
+    if (end == argv[3] || *end) throw std::runtime_error(std::string("bad min_shared: ") + argv[3]);
+    check(sks_ctx_create(0, nullptr, &ctx));
+    sks_sketch_set* db = nullptr;
+    check(sks_sketch_set_load(ctx, argv[2], &db));
+    sks_sketch_info info{};
+    check(sks_sketch_set_info(db, &info));
+    const int nq = argc - 5;
+    sks_sketch_set* q = sketch_files(ctx, nq, argv + 5, info.window, info.mask, info.policy);
+    std::vector<uint32_t> q_sizes(nq);
+    check(sks_sketch_set_sizes(q, q_sizes.data()));
+    FILE* out = std::fopen(argv[4], "w");
+    if (!out) throw std::runtime_error(std::string("cannot write ") + argv[4]);
+    std::fprintf(out, "Query,Round,Reference,Shared,SharedNew,RefSize,FQueryNew,ANI\n");
+    unsigned long long total = 0;
+    for (int i = 0; i < nq; ++i) {
+      // min(references, query elements) records always suffice
+      const uint64_t cap = std::min<uint64_t>(sks_sketch_set_num(db), q_sizes[i]);
+      std::vector<sks_gather_hit> hits(cap);
+      uint64_t n = 0;
+      uint32_t unexplained = 0;
+      void* d_hits = nullptr;
+      check_hip(hipMalloc(&d_hits, (cap ? cap : 1) * sizeof(sks_gather_hit)), "hipMalloc");
+      const int rc = sks_gather_sets(ctx, q, (uint32_t)i, db, (int32_t)min_shared, 0,
+                                     static_cast<sks_gather_hit*>(d_hits), cap, &n, &unexplained);
+      if (rc == SKS_OK && n && sks_ctx_synchronize(ctx) == SKS_OK)
+        check_hip(hipMemcpy(hits.data(), d_hits, n * sizeof(sks_gather_hit), hipMemcpyDeviceToHost), "hipMemcpy");
+      (void)hipFree(d_hits);
+      check(rc);
+      for (uint64_t r = 0; r < n; ++r) {
+        const sks_gather_hit& h = hits[r];
+        const char* ref = sks_sketch_set_name(db, h.ref);
+        const std::string ref_name = ref ? ref : std::to_string(h.ref);
+        std::fprintf(out, "%s,%llu,%s,%d,%d,%d,%.17g,%.17g\n", argv[5 + i], (unsigned long long)r, ref_name.c_str(),
+                     h.shared, h.shared_new, h.ref_size, h.f_query_new, h.ani);
+      }
+      std::fprintf(out, "%s,-,unexplained,%u,,,,\n", argv[5 + i], unexplained);
+      total += n;
+    }
+    std::fclose(out);
+    std::printf("%llu hits -> %s\n", total, argv[4]);
+    sks_sketch_set_free(q);
     sks_sketch_set_free(db);
     sks_ctx_destroy(ctx);
     return 0;

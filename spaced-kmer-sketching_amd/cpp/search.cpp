@@ -86,4 +86,38 @@ std::vector<search_hit> search_hits(const std::vector<kmer_set>& queries, const 
   return out;
 }
 
+std::vector<gather_hit> gather_hits(const kmer_set& query, const std::vector<kmer_set>& refs, int min_shared,
+                                    int max_rounds) {
+  if (max_rounds < 0) throw std::invalid_argument("gather_hits: max_rounds is negative");
+  if (!query.other_masks.empty()) throw std::invalid_argument("gather_hits: a set holds k-mers of several masks");
+  std::vector<gather_hit> out;
+  if (!query.has_mask || query.elements.empty() || refs.empty()) return out;
+  for (const kmer_set& s : refs) {
+    if (!s.other_masks.empty()) throw std::invalid_argument("gather_hits: a set holds k-mers of several masks");
+    if (!s.has_mask || s.elements.empty()) continue;
+    if (!(s.mask == query.mask) || s.window_length != query.window_length)
+      throw std::invalid_argument("gather_hits: the sets differ in mask or window");
+  }
+  const int ew = query.mask.hi() ? 2 : 1;
+  const int k = (int)query.mask.count() / NUCLEOTIDE_BIT_SIZE;
+  if (k <= 0) throw std::invalid_argument("gather_hits: the mask selects no position");
+  sks_ctx* c = ctx();
+  const ResidentSets Q(std::vector<kmer_set>{query}, ew), R(refs, ew);
+  // min(refs, query elements) records always suffice: one call
+  const uint64_t cap = std::min<uint64_t>(R.n, Q.total);
+  DevMem d_hits(cap * sizeof(sks_gather_hit));
+  uint64_t n = 0;
+  check(sks_gather(c, Q.words.as<uint64_t>(), (uint32_t)Q.total, R.words.as<uint64_t>(), R.starts.as<uint64_t>(),
+                   R.sizes.as<uint32_t>(), R.n, R.max_size, R.total, ew, k, min_shared, (uint32_t)max_rounds,
+                   d_hits.as<sks_gather_hit>(), cap, &n, nullptr));
+  check(sks_ctx_synchronize(c));
+  if (!n) return out;
+  std::vector<sks_gather_hit> h(n);
+  check_hip(hipMemcpy(h.data(), d_hits.p, n * sizeof(sks_gather_hit), hipMemcpyDeviceToHost), "D2H");
+  out.reserve(n);
+  for (const sks_gather_hit& x : h)
+    out.push_back(gather_hit{x.ref, x.shared, x.shared_new, x.ref_size, x.f_query_new, x.ani});
+  return out;
+}
+
 }  // namespace sks

@@ -23,4 +23,22 @@ struct search_hit {
 std::vector<search_hit> search_hits(const std::vector<kmer_set>& queries, const std::vector<kmer_set>& refs,
                                     double min_containment, int min_shared);
 
+struct gather_hit {
+  uint32_t ref;        // index into refs
+  int shared;          // kmer_set_intersection(query, refs[ref])
+  int shared_new;      // the query elements this round explains (those no earlier hit held)
+  int ref_size;        // refs[ref].kmer_set_size()
+  double f_query_new;  // containment(shared_new, query.kmer_set_size())
+  double ani;          // binomial_estimator(containment(shared, ref_size), mask.count() / NUCLEOTIDE_BIT_SIZE)
+};
+
+// The greedy min-set cover of `query` by `refs` (sks_gather): each round reports
+// the reference sharing the most still unexplained query k-mers, ties to the
+// smallest index, while that is at least max(min_shared, 1) and fewer than
+// max_rounds rounds were reported (0: no limit), then removes its k-mers from
+// the query.  Hits in round order.  The sets are uploaded once, like
+// search_hits, and must hold k-mers of one common mask.
+std::vector<gather_hit> gather_hits(const kmer_set& query, const std::vector<kmer_set>& refs, int min_shared,
+                                    int max_rounds = 0);
+
 }  // namespace sks

@@ -352,6 +352,12 @@ int sks_ctx_set_search_batch(sks_ctx* c, uint32_t ref_blocks) {
   return SKS_OK;
 }
 
+int sks_ctx_set_gather_rounds(sks_ctx* c, uint32_t rounds_per_wait) {
+  if (!c) return sks::fail(SKS_E_ARG, "sks_ctx_set_gather_rounds: null ctx");
+  c->gather_rounds = rounds_per_wait;
+  return SKS_OK;
+}
+
 // Device time of the last intersection call (after the stream has reached it).
 int sks_ctx_last_intersect_ms(sks_ctx* c, float* ms) {
   if (!c || !ms) return sks::fail(SKS_E_ARG, "null argument");

@@ -1,6 +1,6 @@
 // What the C-ABI translation units that run on a device share (ctx.cpp,
 // host_mem.cpp, sketch_set.cpp, kmer_list.cpp, build.cpp, build_post.cpp,
-// pairs.cpp, search_api.cpp, cluster_api.cpp, downsample_api.cpp, merge_api.cpp): the context, the sketch set
+// pairs.cpp, search_api.cpp, cluster_api.cpp, gather_api.cpp, downsample_api.cpp, merge_api.cpp): the context, the sketch set
 // and k-mer list with the device blocks they own, the error macros, the
 // metadata arena and small argument helpers.
 #pragma once
@@ -18,6 +18,7 @@
 #include "code_objects.hpp"
 #include "device_mem.hpp"
 #include "downsample.hpp"
+#include "gather.hpp"
 #include "ingress.hpp"
 #include "intersect.hpp"
 #include "join.hpp"
@@ -75,6 +76,7 @@ struct sks_ctx {
   int root_k = 0;                   // 0: no table
   sks::Scratch hits;                // sks_search: unsorted hit records, sort keys and indices
   uint32_t search_batch = 0;        // sks_ctx_set_search_batch (0: from the tile budget)
+  uint32_t gather_rounds = 0;       // sks_ctx_set_gather_rounds (0: kGatherDefaultRounds)
 
   // every Scratch member (a new one is added here, and nowhere else)
   template <class F>

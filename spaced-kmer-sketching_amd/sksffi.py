@@ -76,12 +76,24 @@ EXPORTED = [
     "sks_ctx_set_frac_post", "sks_ctx_last_build_path",
     "sks_search", "sks_search_sets", "sks_ctx_set_search_batch", "sks_sketch_set_downsample",
     "sks_sketch_set_merge", "sks_cluster", "sks_cluster_set",
+    "sks_gather", "sks_gather_sets", "sks_ctx_set_gather_rounds",
 ]
 
 # sks_hit (include/sks.h): one record of Context.search's result
 HIT_DTYPE = np.dtype([("query", "<u4"), ("ref", "<u4"), ("shared", "<i4"), ("query_size", "<i4"),
                       ("containment", "<f8"), ("ani", "<f8")])
 assert HIT_DTYPE.itemsize == 32
+
+
+# sks_gather_hit (include/sks.h): the C structure, and one record of Context.gather's result
+class GatherHit(C.Structure):
+    _fields_ = [("ref", C.c_uint32), ("shared", C.c_int32), ("shared_new", C.c_int32), ("ref_size", C.c_int32),
+                ("f_query_new", C.c_double), ("ani", C.c_double)]
+
+
+GATHER_HIT_DTYPE = np.dtype([("ref", "<u4"), ("shared", "<i4"), ("shared_new", "<i4"), ("ref_size", "<i4"),
+                             ("f_query_new", "<f8"), ("ani", "<f8")])
+assert GATHER_HIT_DTYPE.itemsize == 32 == C.sizeof(GatherHit)
 
 _lib = None
 
@@ -233,6 +245,11 @@ def lib():
     L.sks_cluster.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_double,
                               C.c_int32, vp, vp, C.POINTER(C.c_uint32)]
     L.sks_cluster_set.argtypes = [vp, vp, C.c_double, C.c_int32, vp, vp, C.POINTER(C.c_uint32)]
+    L.sks_gather.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,
+                             C.c_int32, C.c_uint32, vp, C.c_uint64, u64p, C.POINTER(C.c_uint32)]
+    L.sks_gather_sets.argtypes = [vp, vp, C.c_uint32, vp, C.c_int32, C.c_uint32, vp, C.c_uint64, u64p,
+                                  C.POINTER(C.c_uint32)]
+    L.sks_ctx_set_gather_rounds.argtypes = [vp, C.c_uint32]
     _lib = L
     return L
 
@@ -767,6 +784,62 @@ class Context:
         max_size, total) with device pointers, as search_arrays takes a side."""
         return self._cluster(int(side[3]), lambda lab, rep: self.cluster_arrays_raw(
             side, elem_words, kmer_num_ones, min_containment, min_shared, lab, rep))
+
+    def set_gather_rounds(self, rounds_per_wait):
+        """sks_ctx_set_gather_rounds: rounds of gather queued per host wait (0: the engine's choice)."""
+        check(lib().sks_ctx_set_gather_rounds(self.h, C.c_uint32(int(rounds_per_wait))))
+
+    def gather_sets_raw(self, queries, q, refs, min_shared, max_rounds, d_hits, hit_cap, want_unexplained=True):
+        """sks_gather_sets with a caller buffer (device pointer, 0 for a size query;
+        either set may be None); returns (status code, exact number of hits,
+        n_unexplained or None when want_unexplained is False) without raising."""
+        n = C.c_uint64(0xffffffff)
+        un = C.c_uint32(0)
+        rc = lib().sks_gather_sets(self.h, queries.h if queries is not None else None, int(q),
+                                   refs.h if refs is not None else None, int(min_shared), int(max_rounds),
+                                   C.c_void_p(d_hits) if d_hits else None, int(hit_cap), C.byref(n),
+                                   C.byref(un) if want_unexplained else None)
+        return rc, int(n.value), (int(un.value) if want_unexplained else None)
+
+    def gather_arrays_raw(self, query, refs, elem_words, kmer_num_ones, min_shared, max_rounds, d_hits, hit_cap,
+                          want_unexplained=True):
+        """sks_gather with caller buffers: query is (device pointer, q_size), refs
+        (data, starts, sizes, n, max_size, total) as search_arrays takes a side.
+        Returns (status code, number of hits, n_unexplained or None) without raising."""
+        v = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        n = C.c_uint64(0xffffffff)
+        un = C.c_uint32(0)
+        rc = lib().sks_gather(self.h, v(query[0]), int(query[1]), v(refs[0]), v(refs[1]), v(refs[2]), int(refs[3]),
+                              int(refs[4]), int(refs[5]), int(elem_words), int(kmer_num_ones), int(min_shared),
+                              int(max_rounds), v(d_hits), int(hit_cap), C.byref(n),
+                              C.byref(un) if want_unexplained else None)
+        return rc, int(n.value), (int(un.value) if want_unexplained else None)
+
+    def _gather(self, cap, call):
+        import torch
+        cap = max(int(cap), 1)  # min(r_n, q_size) records always suffice
+        buf = torch.empty(cap * GATHER_HIT_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        rc, n, un = call(buf.data_ptr(), cap)
+        check(rc)
+        self.synchronize()
+        return buf.cpu().numpy().view(GATHER_HIT_DTYPE)[:n].copy(), un
+
+    def gather(self, queries, q, refs, min_shared=1, max_rounds=0):
+        """sks_gather_sets: the greedy min-set cover of sketch q of `queries` by the
+        sketches of `refs`.  Each round reports the reference sharing the most
+        still unexplained query elements (ties: the smallest index), at least
+        max(min_shared, 1) of them, and removes its elements from the query;
+        max_rounds 0 is no limit.  Returns (GATHER_HIT_DTYPE array in round
+        order, n_unexplained)."""
+        q_size = int(queries.sizes()[q]) if 0 <= q < queries.n else 0
+        return self._gather(min(refs.n, q_size), lambda d, cap: self.gather_sets_raw(
+            queries, q, refs, min_shared, max_rounds, d, cap))
+
+    def gather_arrays(self, query, refs, elem_words, kmer_num_ones, min_shared=1, max_rounds=0):
+        """sks_gather, the device-array form: query is (device pointer, q_size), refs
+        (data, starts, sizes, n, max_size, total) with device pointers."""
+        return self._gather(min(int(refs[3]), int(query[1])), lambda d, cap: self.gather_arrays_raw(
+            query, refs, elem_words, kmer_num_ones, min_shared, max_rounds, d, cap))
 
     def synth_bases(self, d_out_ptr, n, seed, mut_seed=0, mut_rate=0.0, pos_offset=0):
         check(lib().sks_synth_bases(self.h, C.c_void_p(d_out_ptr), n, seed, mut_seed, mut_rate,
