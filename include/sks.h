@@ -28,7 +28,8 @@ extern "C" {
                               this one (round 5); later additions within 3 (new symbols
                               only): sks_sketch_set_downsample, sks_sketch_set_merge, sks_cluster,
                               sks_cluster_set, sks_gather, sks_gather_sets,
-                              sks_ctx_set_gather_rounds.  2: deduplicated join layout (masks, region
+                              sks_ctx_set_gather_rounds, sks_search_topk,
+                              sks_search_topk_sets.  2: deduplicated join layout (masks, region
                               ends), elem_words on the layout entry points,
                               sks_ctx_set_join_check; later additions within 2 (new symbols
                               only): sks_ani_rows, sks_intersect_layout_ani, sks_host_alloc,
@@ -543,6 +544,77 @@ int sks_search_sets(sks_ctx* ctx, const sks_sketch_set* queries, const sks_sketc
 /* Diagnostics: 64-sketch reference blocks per batch of sks_search (0, the
  * default: the engine's choice, which keeps a batch's count tiles within 256 MiB). */
 int sks_ctx_set_search_batch(sks_ctx* ctx, uint32_t ref_blocks);
+
+/* ---- the k best references per query (no reference equivalent) --------------------------
+ * "For each of my sketches, which k references are closest, best first?"  The
+ * output has a fixed size, q_n * k records, so there is no size query, no sort
+ * of hits and no second pass: the layouts, the reference batches and the joins
+ * into count tiles are those of sks_search, and a selection kernel keeps, per
+ * query, a sorted list of k slots across the batches (q_n * k * 16 bytes of
+ * context scratch), which a last kernel expands into records.
+ * score(q, r) is containment(shared, denominator), shared = |Q_q ∩ R_r|, with
+ * the denominator rank_kind names: the query's size (what sks_search thresholds
+ * on), the reference's (a reference inside a metagenome), or the smaller of the
+ * two (what sks_cluster links on).
+ * Eligibility: reference r is listed for query q only if shared >=
+ * max(min_shared, 1), score >= min_score, and, with skip_same_index set, r != q
+ * (the k-NN graph of one set passed as both sides).  A pair sharing nothing is
+ * never listed; an empty sketch has an empty list and is in nobody's list.
+ * Order: strict and total — the larger score first (compared as the doubles
+ * containment returns), ties to the larger shared, then to the smaller ref.
+ * The k best of a strict total order are unique: the result does not depend on
+ * the batch size, on the order in which tiles arrive or on anything else about
+ * the run.
+ * Output: d_hits[q * k + j] (device, q_n * k records) is the j-th best of query
+ * q for j < d_counts[q]; the remaining slots hold {query = q, ref = UINT32_MAX,
+ * rank = j, everything else 0}.  d_counts[q] (device, q_n x u32, may be NULL) is
+ * the number of filled slots.  Every slot of every query is written on success,
+ * also when r_n == 0; q_n == 0 writes nothing and returns SKS_OK.
+ * ani is ani_of(shared, denominator), the function the search's hit filter
+ * uses: with SKS_RANK_QUERY, (shared, query_size, score, ani) of a record are
+ * the same bits as (shared, query_size, containment, ani) of the sks_hit that
+ * sks_search_sets reports for that pair.
+ * Checked on the host before anything is launched: null ctx (before any device
+ * is touched), null d_hits with q_n > 0, k == 0, NaN min_score, unknown
+ * rank_kind, elem_words not 1 or 2, kmer_num_ones <= 0, null arrays where
+ * entries are needed -> SKS_E_ARG; k > SKS_TOPK_MAX -> SKS_E_UNSUPPORTED
+ * (naming "k"); the limits on elements and blocks are those of sks_search.  A
+ * layout the build could not place -> SKS_E_UNSUPPORTED ("invalid layout"), the
+ * contents of d_hits and d_counts then unspecified.
+ * Everything is queued on the context's stream; the call waits once, at the
+ * end, to read the layouts' status words.  Reference batches follow
+ * sks_ctx_set_search_batch and the 256 MiB tile budget, as in sks_search.
+ * sks_ctx_last_intersect_ms then times the whole call. */
+typedef enum sks_rank_kind {
+  SKS_RANK_QUERY = 0,  /* score = containment(shared, |Q_q|)               */
+  SKS_RANK_REF   = 1,  /* score = containment(shared, |R_r|)               */
+  SKS_RANK_MAX   = 2   /* score = containment(shared, min(|Q_q|, |R_r|))   */
+} sks_rank_kind;
+#define SKS_TOPK_MAX 64
+typedef struct sks_top_hit {   /* 40 bytes */
+  uint32_t query, ref;         /* ref == UINT32_MAX: an empty slot                    */
+  int32_t  shared;             /* |Q_query ∩ R_ref|                                   */
+  int32_t  query_size, ref_size;
+  uint32_t rank;               /* position in the query's list, 0 = best              */
+  double   score;              /* as rank_kind says                                   */
+  double   ani;                /* binomial_estimator(score, kmer_num_ones)            */
+} sks_top_hit;
+/* Device-array form: queries and references exactly as sks_search takes them
+ * (group bounds sampled from the references). */
+int sks_search_topk(sks_ctx* ctx, const uint64_t* d_q_data, const uint64_t* d_q_starts, const uint32_t* d_q_sizes,
+                    uint32_t q_n, uint32_t q_max_size, uint64_t q_total, const uint64_t* d_r_data,
+                    const uint64_t* d_r_starts, const uint32_t* d_r_sizes, uint32_t r_n, uint32_t r_max_size,
+                    uint64_t r_total, int elem_words, int kmer_num_ones, int rank_kind, uint32_t k,
+                    double min_score, int32_t min_shared, int skip_same_index, sks_top_hit* d_hits,
+                    uint32_t* d_counts);
+/* The same for two sketch sets (queries == refs is allowed), with the
+ * compatibility rules and messages of sks_search_sets (bottom-s sets of
+ * different s may be compared) and its bounds: the mask-derived ones first,
+ * once more with bounds sampled from the references if a layout cannot be
+ * placed with them. */
+int sks_search_topk_sets(sks_ctx* ctx, const sks_sketch_set* queries, const sks_sketch_set* refs, int rank_kind,
+                         uint32_t k, double min_score, int32_t min_shared, int skip_same_index,
+                         sks_top_hit* d_hits, uint32_t* d_counts);
 
 /* ---- single-linkage clusters (no reference equivalent) ---------------------------------
  * "Which of these sketches are the same thing?": the connected components of the

@@ -35,6 +35,13 @@
 //       unexplained query k-mers, at least min_shared of them:
 //         Query,Round,Reference,Shared,SharedNew,RefSize,FQueryNew,ANI   (doubles as %.17g)
 //       and after each query's rows one line  Query,-,unexplained,<n_unexplained>,,,,
+//   sks-search top <db.sks> <k> <out.csv> <q.fa> ...
+//       each FASTA file is one query, sketched with the database's window, mask
+//       and policy; its k best references (k <= 64), best first, by containment
+//       of the shared k-mers in the query (sks_search_topk_sets, SKS_RANK_QUERY;
+//       ties to the larger Shared, then to the earlier reference); a query with
+//       fewer than k references sharing a k-mer has fewer rows:
+//         Query,Rank,Reference,Shared,Score,ANI     (doubles as %.17g)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -95,8 +102,9 @@ int usage(const char* argv0) {
                "       %s downsample <in.sks> <c> <out.sks>\n"
                "       %s merge <out.sks> <groups.tsv> <in.sks> [<in.sks> ...]\n"
                "       %s cluster <db.sks> <min_containment> <out.tsv> [<reps.sks>]\n"
-               "       %s gather <db.sks> <min_shared> <out.csv> <fasta files...>\n",
-               argv0, argv0, argv0, argv0, argv0, argv0);
+               "       %s gather <db.sks> <min_shared> <out.csv> <fasta files...>\n"
+               "       %s top <db.sks> <k> <out.csv> <fasta files...>\n",
+               argv0, argv0, argv0, argv0, argv0, argv0, argv0);
   return 64;
 }
 
@@ -324,6 +332,46 @@ int run(int argc, char* argv[]) {
       }
       std::fprintf(out, "%s,-,unexplained,%u,,,,\n", argv[5 + i], unexplained);
       total += n;
+    }
+    std::fclose(out);
+    std::printf("%llu hits -> %s\n", total, argv[4]);
+    sks_sketch_set_free(q);
+    sks_sketch_set_free(db);
+    sks_ctx_destroy(ctx);
+    return 0;
+  }
+  if (mode == "top" && argc >= 6) {
+    char* end = nullptr;
+    const unsigned long k = std::strtoul(argv[3], &end, 10);
+    if (end == argv[3] || *end || k == 0 || k > SKS_TOPK_MAX)
+      throw std::runtime_error(std::string("bad k (1 .. ") + std::to_string(SKS_TOPK_MAX) + "): " + argv[3]);
+    check(sks_ctx_create(0, nullptr, &ctx));
+    sks_sketch_set* db = nullptr;
+    check(sks_sketch_set_load(ctx, argv[2], &db));
+    sks_sketch_info info{};
+    check(sks_sketch_set_info(db, &info));
+    const int nq = argc - 5;
+    sks_sketch_set* q = sketch_files(ctx, nq, argv + 5, info.window, info.mask, info.policy);
+    std::vector<sks_top_hit> hits((size_t)nq * k);
+    void* d_hits = nullptr;
+    check_hip(hipMalloc(&d_hits, hits.size() * sizeof(sks_top_hit)), "hipMalloc");
+    const int rc = sks_search_topk_sets(ctx, q, db, SKS_RANK_QUERY, (uint32_t)k, 0.0, 1, 0,
+                                        static_cast<sks_top_hit*>(d_hits), nullptr);
+    if (rc == SKS_OK && sks_ctx_synchronize(ctx) == SKS_OK)
+      check_hip(hipMemcpy(hits.data(), d_hits, hits.size() * sizeof(sks_top_hit), hipMemcpyDeviceToHost), "hipMemcpy");
+    (void)hipFree(d_hits);
+    check(rc);
+    FILE* out = std::fopen(argv[4], "w");
+    if (!out) throw std::runtime_error(std::string("cannot write ") + argv[4]);
+    std::fprintf(out, "Query,Rank,Reference,Shared,Score,ANI\n");
+    unsigned long long total = 0;
+    for (const sks_top_hit& h : hits) {
+      if (h.ref == UINT32_MAX) continue;  // an empty slot
+      const char* ref = sks_sketch_set_name(db, h.ref);
+      const std::string ref_name = ref ? ref : std::to_string(h.ref);
+      std::fprintf(out, "%s,%u,%s,%d,%.17g,%.17g\n", argv[5 + h.query], h.rank, ref_name.c_str(), h.shared, h.score,
+                   h.ani);
+      ++total;
     }
     std::fclose(out);
     std::printf("%llu hits -> %s\n", total, argv[4]);

@@ -1,6 +1,6 @@
 // What the C-ABI translation units that run on a device share (ctx.cpp,
 // host_mem.cpp, sketch_set.cpp, kmer_list.cpp, build.cpp, build_post.cpp,
-// pairs.cpp, search_api.cpp, cluster_api.cpp, gather_api.cpp, downsample_api.cpp, merge_api.cpp): the context, the sketch set
+// pairs.cpp, search_api.cpp, topk_api.cpp, cluster_api.cpp, gather_api.cpp, downsample_api.cpp, merge_api.cpp): the context, the sketch set
 // and k-mer list with the device blocks they own, the error macros, the
 // metadata arena and small argument helpers.
 #pragma once
@@ -29,6 +29,7 @@
 #include "search_kernels.hpp"
 #include "sks.h"
 #include "sks_api_internal.hpp"
+#include "topk.hpp"
 #include "windows.hpp"
 
 #define SKS_HIP(expr)                                                                   \

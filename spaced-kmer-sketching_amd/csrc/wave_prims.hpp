@@ -23,6 +23,15 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t x, uint32_t l) {
   return ((uint64_t)hi << 32) | lo;
 }
 
+// The wave moved up by one lane: lane l receives lane l - 1's v, lane 0 keeps its
+// own (DPP wave_shr:1, one VALU move across all four rows; no LDS)
+__device__ __forceinline__ uint32_t wave_shr1(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138, 0xf, 0xf, false);  // wave_shr:1
+}
+__device__ __forceinline__ uint64_t wave_shr1_64(uint64_t x) {
+  return ((uint64_t)wave_shr1((uint32_t)(x >> 32)) << 32) | wave_shr1((uint32_t)x);
+}
+
 // Exclusive prefix sum of one count per thread over a workgroup of WAVES
 // waves (wsum: WAVES words of LDS); *total (optional) = the sum.  One barrier;
 // none after the reads of wsum, so a caller that writes wsum again (another

@@ -77,12 +77,20 @@ EXPORTED = [
     "sks_search", "sks_search_sets", "sks_ctx_set_search_batch", "sks_sketch_set_downsample",
     "sks_sketch_set_merge", "sks_cluster", "sks_cluster_set",
     "sks_gather", "sks_gather_sets", "sks_ctx_set_gather_rounds",
+    "sks_search_topk", "sks_search_topk_sets",
 ]
 
 # sks_hit (include/sks.h): one record of Context.search's result
 HIT_DTYPE = np.dtype([("query", "<u4"), ("ref", "<u4"), ("shared", "<i4"), ("query_size", "<i4"),
                       ("containment", "<f8"), ("ani", "<f8")])
 assert HIT_DTYPE.itemsize == 32
+
+# sks_rank_kind, SKS_TOPK_MAX and sks_top_hit (include/sks.h): one slot of Context.search_topk's result
+SKS_RANK_QUERY, SKS_RANK_REF, SKS_RANK_MAX = 0, 1, 2
+SKS_TOPK_MAX = 64
+TOP_HIT_DTYPE = np.dtype([("query", "<u4"), ("ref", "<u4"), ("shared", "<i4"), ("query_size", "<i4"),
+                          ("ref_size", "<i4"), ("rank", "<u4"), ("score", "<f8"), ("ani", "<f8")])
+assert TOP_HIT_DTYPE.itemsize == 40
 
 
 # sks_gather_hit (include/sks.h): the C structure, and one record of Context.gather's result
@@ -250,6 +258,10 @@ def lib():
     L.sks_gather_sets.argtypes = [vp, vp, C.c_uint32, vp, C.c_int32, C.c_uint32, vp, C.c_uint64, u64p,
                                   C.POINTER(C.c_uint32)]
     L.sks_ctx_set_gather_rounds.argtypes = [vp, C.c_uint32]
+    L.sks_search_topk.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, C.c_uint32,
+                                  C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_double,
+                                  C.c_int32, C.c_int, vp, vp]
+    L.sks_search_topk_sets.argtypes = [vp, vp, vp, C.c_int, C.c_uint32, C.c_double, C.c_int32, C.c_int, vp, vp]
     _lib = L
     return L
 
@@ -740,6 +752,54 @@ class Context:
                                     C.c_void_p(buf.data_ptr()), cap, C.byref(n)))
         self.synchronize()
         return buf.cpu().numpy().view(HIT_DTYPE)[:int(n.value)].copy()
+
+    def search_topk_sets_raw(self, queries, refs, rank, k, min_score, min_shared, skip_same_index, d_hits, d_counts):
+        """sks_search_topk_sets with caller buffers (device pointers, 0 for NULL;
+        either set may be None); returns the status code without raising."""
+        v = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        return lib().sks_search_topk_sets(self.h, queries.h if queries is not None else None,
+                                          refs.h if refs is not None else None, int(rank), int(k), float(min_score),
+                                          int(min_shared), int(bool(skip_same_index)), v(d_hits), v(d_counts))
+
+    def search_topk_arrays_raw(self, q, r, elem_words, kmer_num_ones, rank, k, min_score, min_shared,
+                               skip_same_index, d_hits, d_counts):
+        """sks_search_topk with caller buffers: q and r as search_arrays takes its
+        sides.  Returns the status code without raising."""
+        v = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        return lib().sks_search_topk(self.h, v(q[0]), v(q[1]), v(q[2]), int(q[3]), int(q[4]), int(q[5]),
+                                     v(r[0]), v(r[1]), v(r[2]), int(r[3]), int(r[4]), int(r[5]), int(elem_words),
+                                     int(kmer_num_ones), int(rank), int(k), float(min_score), int(min_shared),
+                                     int(bool(skip_same_index)), v(d_hits), v(d_counts))
+
+    def _search_topk(self, q_n, k, call):
+        import torch
+        dev = torch.device("cuda", self.device)
+        slots = int(q_n) * max(int(k), 0)
+        buf = torch.empty(max(slots, 1) * TOP_HIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        cnt = torch.empty(max(int(q_n), 1), dtype=torch.int32, device=dev)
+        check(call(buf.data_ptr(), cnt.data_ptr()))
+        self.synchronize()
+        hits = buf.cpu().numpy().view(TOP_HIT_DTYPE)[:slots].copy().reshape(int(q_n), int(k))
+        return hits, cnt.cpu().numpy().view(np.uint32)[:int(q_n)].copy()
+
+    def search_topk(self, queries, refs, k, rank=SKS_RANK_QUERY, min_score=0.0, min_shared=1, skip_same_index=False):
+        """sks_search_topk_sets: for every sketch of `queries` its k best sketches
+        of `refs`, best first, by containment of the shared k-mers in the query
+        (SKS_RANK_QUERY), in the reference (SKS_RANK_REF) or in the smaller of the
+        two (SKS_RANK_MAX); ties go to the larger shared, then the smaller ref.
+        Listed are references sharing at least max(min_shared, 1) k-mers with
+        score >= min_score, and with skip_same_index not the query's own index.
+        Returns (hits TOP_HIT_DTYPE[q_n, k], counts u32[q_n]): row q holds
+        counts[q] records, then empty slots (ref 0xffffffff)."""
+        return self._search_topk(queries.n, k, lambda d, n: self.search_topk_sets_raw(
+            queries, refs, rank, k, min_score, min_shared, skip_same_index, d, n))
+
+    def search_topk_arrays(self, q, r, elem_words, kmer_num_ones, k, rank=SKS_RANK_QUERY, min_score=0.0,
+                           min_shared=1, skip_same_index=False):
+        """sks_search_topk, the device-array form: q and r are (data, starts, sizes,
+        n, max_size, total) with device pointers, as search_arrays takes them."""
+        return self._search_topk(int(q[3]), k, lambda d, n: self.search_topk_arrays_raw(
+            q, r, elem_words, kmer_num_ones, rank, k, min_score, min_shared, skip_same_index, d, n))
 
     def cluster_set_raw(self, sketch_set, min_containment, min_shared, d_cluster, d_rep):
         """sks_cluster_set with caller buffers (device pointers, 0 for NULL; the set
