@@ -11,16 +11,7 @@ namespace {
 // packed count tiles of one batch of column blocks (16 KB a tile), as the search's
 constexpr uint64_t kClusterTileBudget = 256ull << 20;
 
-struct ClusterSide {
-  const uint64_t* data;
-  const uint64_t* starts;
-  const uint32_t* sizes;
-  uint32_t n, max_size;
-  uint64_t total;
-};
-
-// h_bounds: the host group bounds to use ((G + 1) * ew words for the log_b
-// below), or null to sample them from the set.
+// h_bounds, invalid_layout: as the core of with_mask_bounds_retry (null: sampled from the set).
 //
 // The set is joined with itself and the link rule is symmetric, so ONE layout
 // serves rows and columns and only the tiles (I, J), I <= J, are joined.  The
@@ -29,16 +20,14 @@ struct ClusterSide {
 // buffer and linked before the next batch clears it.  Batches bound the count
 // tiles, never the layout: the layout of the whole set is needed for the rows
 // of every batch anyway, so no batch builds one of its own.
-int cluster_core(sks_ctx* c, const char* who, const ClusterSide& S, int ew, double min_containment,
+int cluster_core(sks_ctx* c, const char* who, const SketchSpan& S, int ew, double min_containment,
                  int32_t min_shared, const std::vector<uint64_t>* h_bounds, uint32_t* d_cluster, uint32_t* d_rep,
                  uint32_t* n_clusters, bool* invalid_layout = nullptr) {
   const std::string me(who);
   *n_clusters = 0;
-  if (invalid_layout) *invalid_layout = false;
   if (S.n == 0) return SKS_OK;
   DeviceGuard g(c->device);
   const uint32_t log_b = sks::join_log_b(std::max<uint32_t>(S.max_size, 1));
-  const uint32_t G = sks::join_layout_groups(log_b);
   const uint32_t nb = (S.n + 63) / 64;
   const uint64_t tiles_all = cluster_tiles_before(nb);
   if (tiles_all > 0x7fffffffull) return sks::fail(SKS_E_UNSUPPORTED, me + ": too many 64-sketch blocks");
@@ -58,7 +47,7 @@ int cluster_core(sks_ctx* c, const char* who, const ClusterSide& S, int ew, doub
   // tile list, one batch's packed counts, parent / root / id (n words each), the
   // representative keys, the roots per chunk and the layout build's temporary storage
   Carver cv;
-  const Region<uint64_t> r_bounds = cv.take<uint64_t>((size_t)(G + 1) * ew);
+  const Region<uint64_t> r_bounds = cv.take<uint64_t>((size_t)(sks::join_layout_groups(log_b) + 1) * ew);
   const LayoutRegions r_lay = carve_layout(cv, S.total, nb, BW, ew);
   const Region<uint32_t> r_stat = cv.take<uint32_t>(4);
   const Region<uint32_t> r_tiles = cv.take<uint32_t>(tiles_all * 2);
@@ -82,10 +71,7 @@ int cluster_core(sks_ctx* c, const char* who, const ClusterSide& S, int ew, doub
     const std::vector<uint32_t> h_tiles = cluster_tile_list(nb);
     SKS_HIP(sks::pinned_h2d(tiles, h_tiles.data(), h_tiles.size() * 4, c->stream));
   }
-  if (h_bounds)
-    SKS_HIP(sks::pinned_h2d(bounds, h_bounds->data(), (size_t)(G + 1) * 8 * ew, c->stream));
-  else
-    SKS_HIP(sks::join_layout_bounds(S.data, S.starts, S.sizes, S.n, log_b, ew, bounds, c->stream));
+  SKS_TRY(queue_group_bounds(c, S, log_b, ew, h_bounds, bounds));
   // the layout, once; its second launch clears the status words, the cluster
   // count and the first batch's tiles
   const ClusterRange first = cluster_batch_range(nb, bb, 0);
@@ -111,11 +97,7 @@ int cluster_core(sks_ctx* c, const char* who, const ClusterSide& S, int ew, doub
   uint32_t h_stat[4] = {0, 0, 0, 0};
   SKS_HIP(sks::pinned_d2h(h_stat, stat, sizeof h_stat, c->stream));
   SKS_HIP(hipEventRecord(c->ev_end, c->stream));
-  if (h_stat[1]) {
-    if (invalid_layout) *invalid_layout = true;
-    return sks::fail(SKS_E_UNSUPPORTED, me + ": the join layout of the set could not be placed (invalid layout); "
-                                             "nothing is linked");
-  }
+  if (h_stat[1]) return fail_invalid_layout(me, "the set", "nothing is linked", invalid_layout);
   *n_clusters = h_stat[2];
   return SKS_OK;
 }
@@ -134,8 +116,8 @@ int sks_cluster(sks_ctx* c, const uint64_t* d_data, const uint64_t* d_starts, co
   if (kmer_num_ones <= 0) return sks::fail(SKS_E_ARG, "sks_cluster: kmer_num_ones must be positive");
   if (!(min_containment == min_containment)) return sks::fail(SKS_E_ARG, "sks_cluster: min_containment is NaN");
   if (n && (!d_starts || !d_sizes)) return sks::fail(SKS_E_ARG, "sks_cluster: null argument");
-  if (total >= (1ull << 32)) return sks::fail(SKS_E_UNSUPPORTED, "sks_cluster: >= 2^32 elements in the set");
-  const ClusterSide S{d_data, d_starts, d_sizes, n, max_size, total};
+  SKS_TRY(check_span_totals("sks_cluster", "in the set", total));
+  const SketchSpan S{d_data, d_starts, d_sizes, n, max_size, total, nullptr};
   return cluster_core(c, "sks_cluster", S, elem_words, min_containment, min_shared, nullptr, d_cluster, d_rep,
                       n_clusters);
 }
@@ -148,25 +130,16 @@ int sks_cluster_set(sks_ctx* c, const sks_sketch_set* set, double min_containmen
   if (!(min_containment == min_containment)) return sks::fail(SKS_E_ARG, "sks_cluster_set: min_containment is NaN");
   if (set->device != c->device)
     return sks::fail(SKS_E_ARG, "sks_cluster_set: the set lives on another device than the context");
-  ClusterSide S{set->d_data(), set->d_starts(), set->d_sizes(), set->n, 0, 0};
-  for (uint32_t v : set->sizes) {
-    S.max_size = std::max(S.max_size, v);
-    S.total += v;
-  }
-  if (S.total >= (1ull << 32)) return sks::fail(SKS_E_UNSUPPORTED, "sks_cluster_set: >= 2^32 elements in the set");
+  const SketchSpan S = span_of(set);
+  SKS_TRY(check_span_totals("sks_cluster_set", "in the set", S.total));
   if (S.n == 0) return SKS_OK;
-  // group bounds fixed by the mask: no sampling pass
-  const uint32_t log_b = sks::join_log_b(std::max<uint32_t>(S.max_size, 1));
-  std::vector<uint64_t> h_bounds((size_t)(sks::join_layout_groups(log_b) + 1) * set->elem_words);
-  SKS_TRY(sks_join_layout_bounds_for_mask(set->mask, log_b, set->elem_words, h_bounds.data()));
-  bool invalid = false;
-  const int rc = cluster_core(c, "sks_cluster_set", S, set->elem_words, min_containment, min_shared, &h_bounds,
-                              d_cluster, d_rep, n_clusters, &invalid);
-  if (!invalid) return rc;
-  // k-mers far from uniform overfilled a group of the mask's bounds: once more
-  // with bounds sampled from the set (SKS_E_UNSUPPORTED if that fails too)
-  return cluster_core(c, "sks_cluster_set", S, set->elem_words, min_containment, min_shared, nullptr, d_cluster,
-                      d_rep, n_clusters);
+  // the mask's group bounds; sampled from the set if they cannot place the layout
+  std::vector<uint64_t> mask_bounds;
+  SKS_TRY(mask_group_bounds(set->mask, set->elem_words, S.max_size, &mask_bounds));
+  return with_mask_bounds_retry(mask_bounds, [&](const std::vector<uint64_t>* h_bounds, bool* invalid) {
+    return cluster_core(c, "sks_cluster_set", S, set->elem_words, min_containment, min_shared, h_bounds, d_cluster,
+                        d_rep, n_clusters, invalid);
+  });
 }
 
 }  // extern "C"

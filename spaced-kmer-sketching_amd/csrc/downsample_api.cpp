@@ -10,6 +10,32 @@
 
 using namespace sks;
 
+int sks::reserve_chunk_counters(sks_ctx* c, uint64_t n_chunks) {
+  SKS_HIP(c->flag.reserve((n_chunks + 1) * sizeof(uint32_t)));
+  SKS_HIP(c->pos.reserve((n_chunks + 1) * sizeof(uint64_t)));
+  return SKS_OK;
+}
+
+int sks::size_set_from_counts(sks_ctx* c, const char* who, const char* too_large, uint64_t n_chunks,
+                              const uint64_t* d_chunk_off, const uint32_t* bound, sks_sketch_set* set) {
+  hipStream_t st = c->stream;
+  const uint32_t n = set->n;
+  SKS_HIP(sks::downsample_offsets(chunk_counts(c), n_chunks, chunk_offs(c), d_chunk_off, n, set->d_starts(),
+                                  set->d_sizes(), c->tmp, st));
+  // the wait: the new sizes size the new set's data array exactly
+  std::vector<uint32_t> sizes(n, 0);
+  SKS_HIP(sks::pinned_d2h(sizes.data(), set->d_sizes(), n * sizeof(uint32_t), st));
+  uint64_t total = 0;
+  for (uint32_t g = 0; g < n; ++g) {
+    if (sizes[g] > bound[g]) return sks::fail(SKS_E_HIP, std::string(who) + ": " + too_large);
+    set->starts[g] = total;
+    total += sizes[g];
+  }
+  SKS_TRY(alloc_u64(set->data, total * set->elem_words, st));
+  set->sizes = std::move(sizes);
+  return SKS_OK;
+}
+
 int sks::downsample_arrays(sks_ctx* c, const char* who, const uint64_t* d_data, const uint64_t* d_starts,
                            const uint32_t* d_sizes, const std::vector<uint32_t>& src_sizes, const sks_sketch_set& like,
                            uint64_t param, SetPtr* out) {
@@ -44,10 +70,7 @@ int sks::downsample_arrays(sks_ctx* c, const char* who, const uint64_t* d_data, 
   MetaArena arena(c);
   const size_t o_chunk = arena.add(chunk_off), o_dense = arena.add(dense_off);
   SKS_TRY(arena.upload());
-  SKS_HIP(c->flag.reserve((n_chunks + 1) * sizeof(uint32_t)));
-  SKS_HIP(c->pos.reserve((n_chunks + 1) * sizeof(uint64_t)));
-  uint32_t* d_counts = reinterpret_cast<uint32_t*>(c->flag.ptr);
-  uint64_t* d_offs = reinterpret_cast<uint64_t*>(c->pos.ptr);
+  SKS_TRY(reserve_chunk_counters(c, n_chunks));
 
   DownsampleArgs a{};
   a.data = d_data;
@@ -77,22 +100,11 @@ int sks::downsample_arrays(sks_ctx* c, const char* who, const uint64_t* d_data, 
     a.keep_flag = d_keep;
   }
 
-  SKS_HIP(sks::downsample_count(a, ew, pol.flavour, mode, n, max_len, d_counts, st));
-  SKS_HIP(sks::downsample_offsets(d_counts, n_chunks, d_offs, a.chunk_off, n, set->d_starts(), set->d_sizes(), c->tmp,
-                                  st));
-  // the call's one wait: the new sizes size the new set's data array exactly
-  std::vector<uint32_t> sizes(n, 0);
-  SKS_HIP(sks::pinned_d2h(sizes.data(), set->d_sizes(), n * sizeof(uint32_t), st));
-  uint64_t total = 0;
-  for (uint32_t g = 0; g < n; ++g) {
-    if (sizes[g] > src_sizes[g])
-      return sks::fail(SKS_E_HIP, std::string(who) + ": a filtered sketch is larger than its source");
-    set->starts[g] = total;
-    total += sizes[g];
-  }
-  SKS_TRY(alloc_u64(set->data, total * ew, st));
-  set->sizes = sizes;
-  SKS_HIP(sks::downsample_scatter(a, ew, pol.flavour, mode, n, max_len, d_offs, set->d_data(), st));
+  SKS_HIP(sks::downsample_count(a, ew, pol.flavour, mode, n, max_len, chunk_counts(c), st));
+  // the call's one wait
+  SKS_TRY(size_set_from_counts(c, who, "a filtered sketch is larger than its source", n_chunks, a.chunk_off,
+                               src_sizes.data(), set.get()));
+  SKS_HIP(sks::downsample_scatter(a, ew, pol.flavour, mode, n, max_len, chunk_offs(c), set->d_data(), st));
   *out = std::move(set);
   return SKS_OK;
 }

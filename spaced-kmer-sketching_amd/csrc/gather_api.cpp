@@ -7,15 +7,7 @@ using namespace sks;
 
 namespace {
 
-struct GatherRefs {
-  const uint64_t* data;
-  const uint64_t* starts;
-  const uint32_t* sizes;
-  uint32_t n;
-  uint64_t total;
-};
-
-int gather_core(sks_ctx* c, const char* who, const uint64_t* d_q, uint32_t q_size, const GatherRefs& R, int ew,
+int gather_core(sks_ctx* c, const char* who, const uint64_t* d_q, uint32_t q_size, const SketchSpan& R, int ew,
                 int kmer_num_ones, int32_t min_shared, uint32_t max_rounds, sks_gather_hit* d_hits,
                 uint64_t hit_cap, uint64_t* n_hits, uint32_t* n_unexplained) {
   const std::string me(who);
@@ -107,7 +99,6 @@ int sks_gather(sks_ctx* c, const uint64_t* d_q, uint32_t q_size, const uint64_t*
                const uint64_t* d_r_starts, const uint32_t* d_r_sizes, uint32_t r_n, uint32_t r_max_size,
                uint64_t r_total, int elem_words, int kmer_num_ones, int32_t min_shared, uint32_t max_rounds,
                sks_gather_hit* d_hits, uint64_t hit_cap, uint64_t* n_hits, uint32_t* n_unexplained) {
-  (void)r_max_size;  // taken for symmetry with sks_search: a workgroup walks a reference whatever its size
   if (n_hits) *n_hits = 0;
   if (!c) return sks::fail(SKS_E_ARG, "sks_gather: null ctx");
   if (!n_hits) return sks::fail(SKS_E_ARG, "sks_gather: null n_hits");
@@ -115,8 +106,9 @@ int sks_gather(sks_ctx* c, const uint64_t* d_q, uint32_t q_size, const uint64_t*
   if (kmer_num_ones <= 0) return sks::fail(SKS_E_ARG, "sks_gather: kmer_num_ones must be positive");
   if ((q_size && !d_q) || (r_n && (!d_r_starts || !d_r_sizes)) || (r_n && r_total && !d_r_data))
     return sks::fail(SKS_E_ARG, "sks_gather: null argument");
-  if (r_total >= (1ull << 32)) return sks::fail(SKS_E_UNSUPPORTED, "sks_gather: >= 2^32 elements in the references");
-  const GatherRefs R{d_r_data, d_r_starts, d_r_sizes, r_n, r_total};
+  SKS_TRY(check_span_totals("sks_gather", "in the references", r_total));
+  // r_max_size is taken for symmetry with sks_search: a workgroup walks a reference whatever its size
+  const SketchSpan R{d_r_data, d_r_starts, d_r_sizes, r_n, r_max_size, r_total, nullptr};
   return gather_core(c, "sks_gather", d_q, q_size, R, elem_words, kmer_num_ones, min_shared, max_rounds, d_hits,
                      hit_cap, n_hits, n_unexplained);
 }
@@ -130,30 +122,14 @@ int sks_gather_sets(sks_ctx* c, const sks_sketch_set* queries, uint32_t q, const
   if (q >= queries->n)
     return sks::fail(SKS_E_ARG, "sks_gather_sets: query index " + std::to_string(q) + " out of range (" +
                                     std::to_string(queries->n) + " sketches)");
-  sks_sketch_info qi{}, ri{};
-  SKS_TRY(sks_sketch_set_info(queries, &qi));
-  SKS_TRY(sks_sketch_set_info(refs, &ri));
-  const char* field = nullptr;
-  if (qi.window != ri.window) field = "window";
-  else if (qi.mask[0] != ri.mask[0] || qi.mask[1] != ri.mask[1]) field = "mask";
-  else if (qi.elem_words != ri.elem_words) field = "elem_words";
-  else if (qi.policy.kind != ri.policy.kind) field = "policy kind";
-  else if (qi.policy.flavour != ri.policy.flavour) field = "hash flavour";
-  else if (qi.policy.nonce != ri.policy.nonce) field = "nonce";
-  else if (qi.policy.kind == SKS_FRAC_MOD && qi.policy.param != ri.policy.param) field = "policy param (FracMinHash c)";
-  if (field)
-    return sks::fail(SKS_E_ARG, std::string("sks_gather_sets: the query and reference sets differ in ") + field);
+  sks_sketch_info qi{};
+  int k = 0;
   // subtraction only means something when every sketch samples the same hash space
-  if (qi.policy.kind != SKS_FRAC_MOD)
-    return sks::fail(SKS_E_ARG, "sks_gather_sets: the sets' policy kind must be SKS_FRAC_MOD (a bottom-s sketch "
-                                "samples a hash range of its own)");
-  if (queries->device != c->device || refs->device != c->device)
-    return sks::fail(SKS_E_ARG, "sks_gather_sets: a set lives on another device than the context");
-  const int k = (__builtin_popcountll(qi.mask[0]) + __builtin_popcountll(qi.mask[1])) / 2;
-  if (k <= 0) return sks::fail(SKS_E_ARG, "sks_gather_sets: the sets' mask selects no position");
-  GatherRefs R{refs->d_data(), refs->d_starts(), refs->d_sizes(), refs->n, 0};
-  for (uint32_t v : refs->sizes) R.total += v;
-  if (R.total >= (1ull << 32)) return sks::fail(SKS_E_UNSUPPORTED, "sks_gather_sets: >= 2^32 elements in the references");
+  SKS_TRY(search_sets_compatible(c, "sks_gather_sets", queries, refs, &qi, &k,
+                                 "the sets' policy kind must be SKS_FRAC_MOD (a bottom-s sketch samples a hash range "
+                                 "of its own)"));
+  const SketchSpan R = span_of(refs);
+  SKS_TRY(check_span_totals("sks_gather_sets", "in the references", R.total));
   const uint64_t* d_q = queries->d_data() + queries->starts[q] * (uint64_t)qi.elem_words;
   return gather_core(c, "sks_gather_sets", d_q, queries->sizes[q], R, qi.elem_words, k, min_shared, max_rounds,
                      d_hits, hit_cap, n_hits, n_unexplained);

@@ -13,17 +13,6 @@ const char* const kWho = "sks_sketch_set_merge";
 
 int refuse(const std::string& what) { return sks::fail(SKS_E_ARG, std::string(kWho) + ": " + what); }
 
-// The field two sets differ in, or null.
-const char* differing_field(const sks_sketch_set* a, const sks_sketch_set* b) {
-  if (b->window != a->window) return "window";
-  if (b->mask[0] != a->mask[0] || b->mask[1] != a->mask[1] || b->elem_words != a->elem_words) return "mask";
-  if (b->policy.kind != a->policy.kind) return "policy kind";
-  if (b->policy.flavour != a->policy.flavour) return "flavour";
-  if (b->policy.nonce != a->policy.nonce) return "nonce";
-  if (a->policy.kind != SKS_BOTTOM_S && b->policy.param != a->policy.param) return "policy param";
-  return nullptr;
-}
-
 }  // namespace
 
 extern "C" int sks_sketch_set_merge(sks_ctx* c, const sks_sketch_set* const* sets, uint32_t n_sets,
@@ -44,7 +33,7 @@ extern "C" int sks_sketch_set_merge(sks_ctx* c, const sks_sketch_set* const* set
     if (b->device != c->device)
       return refuse("set " + std::to_string(i) + " is on device " + std::to_string(b->device) +
                     ", the context on device " + std::to_string(c->device));
-    if (const char* f = differing_field(first, b))
+    if (const char* f = set_differs_in(info_of(*first), info_of(*b), ParamRule::kFracOnly))
       return refuse("set " + std::to_string(i) + " differs from set 0 in " + f);
     policy.param = std::min(policy.param, b->policy.param);  // bottom-s: the smallest s
   }
@@ -124,6 +113,7 @@ extern "C" int sks_sketch_set_merge(sks_ctx* c, const sks_sketch_set* const* set
   }
   // where every group's one run lies, and the duplicate filter's chunks
   std::vector<uint64_t> runs(2 * (size_t)n_groups, 0), chunk_off(n_groups + 1, 0);
+  std::vector<uint32_t> run_len(n_groups, 0);  // a union holds no more than its members (each sum fits 32 bits)
   for (uint32_t g = 0; g < n_groups; ++g) {
     const MergeFinal& f = plan.final_run[g];
     if (f.round >= 0)
@@ -131,6 +121,7 @@ extern "C" int sks_sketch_set_merge(sks_ctx* c, const sks_sketch_set* const* set
     else if (f.run != kMergeNoRun)
       runs[2 * g] = src_addr[members[f.run]];
     runs[2 * g + 1] = f.len;
+    run_len[g] = (uint32_t)f.len;
     chunk_off[g + 1] = chunk_off[g] + tiles_of(f.len, kDownsampleChunk);
   }
   const uint64_t n_chunks = chunk_off[n_groups];
@@ -140,36 +131,22 @@ extern "C" int sks_sketch_set_merge(sks_ctx* c, const sks_sketch_set* const* set
   SetPtr set;
   SKS_TRY(make_sketch_set(c->device, ew, first->window, first->mask, policy, std::vector<uint32_t>(n_groups, 0),
                           windows, {}, nullptr, st, MetaUpload::kNone, &set));
-  SKS_HIP(c->flag.reserve((n_chunks + 1) * sizeof(uint32_t)));
-  SKS_HIP(c->pos.reserve((n_chunks + 1) * sizeof(uint64_t)));
-  uint32_t* d_counts = reinterpret_cast<uint32_t*>(c->flag.ptr);
-  uint64_t* d_offs = reinterpret_cast<uint64_t*>(c->pos.ptr);
+  SKS_TRY(reserve_chunk_counters(c, n_chunks));
 
   for (size_t r = 0; r < plan.rounds.size(); ++r) {
     const MergeRound& R = plan.rounds[r];
     SKS_HIP(sks::merge_round(arena.ptr(at[r].pairs), arena.ptr(at[r].tiles), (uint32_t)R.pairs.size(),
                              R.tile_off.back(), ew, st));
   }
-  SKS_HIP(sks::merge_unique_count(arena.ptr(o_runs), arena.ptr(o_chunk), n_groups, n_chunks, ew, d_counts, st));
-  SKS_HIP(sks::downsample_offsets(d_counts, n_chunks, d_offs, arena.ptr(o_chunk), n_groups, set->d_starts(),
-                                  set->d_sizes(), c->tmp, st));
-  // the first wait: the distinct sizes size the new set's data array exactly
-  std::vector<uint32_t> sizes(n_groups, 0);
-  SKS_HIP(sks::pinned_d2h(sizes.data(), set->d_sizes(), n_groups * sizeof(uint32_t), st));
-  uint64_t total = 0;
-  bool cut = false;  // bottom-s: a union holds more than s elements
-  for (uint32_t g = 0; g < n_groups; ++g) {
-    if (sizes[g] > plan.final_run[g].len)
-      return sks::fail(SKS_E_HIP, std::string(kWho) + ": a union is larger than its members");
-    set->starts[g] = total;
-    total += sizes[g];
-    cut = cut || (bottom && sizes[g] > policy.param);
-  }
-  SKS_TRY(alloc_u64(set->data, total * ew, st));
-  set->sizes = sizes;
-  SKS_HIP(sks::merge_unique_scatter(arena.ptr(o_runs), arena.ptr(o_chunk), n_groups, n_chunks, ew, d_offs,
+  SKS_HIP(sks::merge_unique_count(arena.ptr(o_runs), arena.ptr(o_chunk), n_groups, n_chunks, ew, chunk_counts(c),
+                                  st));
+  // the first wait
+  SKS_TRY(size_set_from_counts(c, kWho, "a union is larger than its members", n_chunks, arena.ptr(o_chunk),
+                               run_len.data(), set.get()));
+  SKS_HIP(sks::merge_unique_scatter(arena.ptr(o_runs), arena.ptr(o_chunk), n_groups, n_chunks, ew, chunk_offs(c),
                                     set->d_data(), st));
-  if (cut) {
+  const auto over_s = [&](uint32_t v) { return v > policy.param; };  // bottom-s: a union holds more than s elements
+  if (bottom && std::any_of(set->sizes.begin(), set->sizes.end(), over_s)) {
     // the second wait; the uncut set goes back to the block cache behind the queued filter
     SetPtr kept;
     SKS_TRY(downsample_arrays(c, kWho, set->d_data(), set->d_starts(), set->d_sizes(), set->sizes, *set, policy.param,

@@ -4,8 +4,7 @@
 // built with the query layout's log_b and group bounds and joined with it into
 // packed count tiles [b_blocks][q_blocks][64][64] (tile bj * q_blocks + qi, rows
 // = queries), which the caller's kernel consumes before the next batch clears
-// them; one wait at the end reads every layout's status words.  Also the
-// compatibility rules of the two calls' set forms.
+// them; one wait at the end reads every layout's status words.
 #pragma once
 #include "sks_ctx.hpp"
 
@@ -14,50 +13,6 @@ namespace sks {
 // packed count tiles of one reference batch (16 KB a tile): the default batch is
 // the largest number of reference blocks whose tiles fit
 constexpr uint64_t kSearchTileBudget = 256ull << 20;
-
-struct SearchSide {
-  const uint64_t* data;
-  const uint64_t* starts;
-  const uint32_t* sizes;
-  uint32_t n, max_size;
-  uint64_t total;
-  const uint32_t* h_sizes;  // host copy of the sizes, or null (batches are then sized by max_size)
-};
-
-inline SearchSide search_side_of(const sks_sketch_set* s) {
-  SearchSide S{s->d_data(), s->d_starts(), s->d_sizes(), s->n, 0, 0, s->sizes.data()};
-  for (uint32_t v : s->sizes) {
-    S.max_size = std::max(S.max_size, v);
-    S.total += v;
-  }
-  return S;
-}
-
-// Two sets one of these calls may compare: the same window, mask, elem_words,
-// policy kind, hash flavour and nonce, and for SKS_FRAC_MOD the policy param,
-// both on the context's device.  *info: the queries'; *kmer_num_ones from the mask.
-inline int search_sets_compatible(const sks_ctx* c, const std::string& me, const sks_sketch_set* queries,
-                                  const sks_sketch_set* refs, sks_sketch_info* info, int* kmer_num_ones) {
-  sks_sketch_info qi{}, ri{};
-  SKS_TRY(sks_sketch_set_info(queries, &qi));
-  SKS_TRY(sks_sketch_set_info(refs, &ri));
-  const char* field = nullptr;
-  if (qi.window != ri.window) field = "window";
-  else if (qi.mask[0] != ri.mask[0] || qi.mask[1] != ri.mask[1]) field = "mask";
-  else if (qi.elem_words != ri.elem_words) field = "elem_words";
-  else if (qi.policy.kind != ri.policy.kind) field = "policy kind";
-  else if (qi.policy.flavour != ri.policy.flavour) field = "hash flavour";
-  else if (qi.policy.nonce != ri.policy.nonce) field = "nonce";
-  else if (qi.policy.kind == SKS_FRAC_MOD && qi.policy.param != ri.policy.param) field = "policy param (FracMinHash c)";
-  if (field) return sks::fail(SKS_E_ARG, me + ": the query and reference sets differ in " + field);
-  if (queries->device != c->device || refs->device != c->device)
-    return sks::fail(SKS_E_ARG, me + ": a set lives on another device than the context");
-  const int k = (__builtin_popcountll(qi.mask[0]) + __builtin_popcountll(qi.mask[1])) / 2;
-  if (k <= 0) return sks::fail(SKS_E_ARG, me + ": the sets' mask selects no position");
-  *info = qi;
-  *kmer_num_ones = k;
-  return SKS_OK;
-}
 
 // One call's walk.  plan() sizes the batches and carves c->lay: the group
 // bounds, the query layout, one batch's layout, `head_words` words of the
@@ -92,7 +47,7 @@ struct SearchWalk {
   // after end()
   std::vector<uint32_t> h_span;
 
-  int plan(sks_ctx* c, const std::string& me, const SearchSide& Q, const SearchSide& R, int elem_words,
+  int plan(sks_ctx* c, const std::string& me, const SketchSpan& Q, const SketchSpan& R, int elem_words,
            size_t caller_head_words, size_t extra_bytes) {
     ew = elem_words;
     log_b = sks::join_log_b(std::max<uint32_t>(std::max(Q.max_size, R.max_size), 1));
@@ -155,7 +110,7 @@ struct SearchWalk {
 
   // h_bounds: the host group bounds to use ((G + 1) * ew words for log_b), or
   // null to sample them once from the references.
-  int begin(sks_ctx* c, const SearchSide& Q, const SearchSide& R, const std::vector<uint64_t>* h_bounds) {
+  int begin(sks_ctx* c, const SketchSpan& Q, const SketchSpan& R, const std::vector<uint64_t>* h_bounds) {
     SKS_HIP(hipEventRecord(c->ev_begin, c->stream));
     SKS_HIP(hipMemsetAsync(head, 0, span_words * 4, c->stream));
     // tile bj * qb + qi = (query block qi, batch block bj): queries are global
@@ -170,10 +125,7 @@ struct SearchWalk {
         }
       SKS_HIP(sks::pinned_h2d(tiles, h_tiles.data(), h_tiles.size() * 4, c->stream));
     }
-    if (h_bounds)
-      SKS_HIP(sks::pinned_h2d(bounds, h_bounds->data(), (size_t)(G + 1) * 8 * ew, c->stream));
-    else
-      SKS_HIP(sks::join_layout_bounds(R.data, R.starts, R.sizes, R.n, log_b, ew, bounds, c->stream));
+    SKS_TRY(queue_group_bounds(c, R, log_b, ew, h_bounds, bounds));
     // the query layout, once
     SKS_HIP(sks::join_layout_build(Q.data, Q.starts, Q.sizes, Q.n, log_b, ew, bounds, tmp, AQ.vals, AQ.masks, AQ.boff,
                                    AQ.bstart, stat, c->join_check, c->stream));
@@ -181,7 +133,7 @@ struct SearchWalk {
   }
 
   // batch b: references [r0, r0 + rn) in nbb blocks, their counts in cnt
-  int batch(sks_ctx* c, const SearchSide& R, uint32_t b) {
+  int batch(sks_ctx* c, const SketchSpan& R, uint32_t b) {
     r0 = (uint32_t)(b * bb * 64);
     rn = (uint32_t)std::min<uint64_t>(R.n - r0, bb * 64);
     nbb = (rn + 63) / 64;
@@ -209,11 +161,8 @@ struct SearchWalk {
     for (uint32_t b = 0; b <= n_batches; ++b)
       if (h_span[head_words + 2 * b + 1]) {
         SKS_HIP(hipEventRecord(c->ev_end, c->stream));
-        if (invalid_layout) *invalid_layout = true;
-        return sks::fail(SKS_E_UNSUPPORTED,
-                         me + ": the join layout of " +
-                             (b ? "reference batch " + std::to_string(b - 1) : std::string("the queries")) +
-                             " could not be placed (invalid layout); " + nothing);
+        return fail_invalid_layout(me, b ? "reference batch " + std::to_string(b - 1) : std::string("the queries"),
+                                   nothing, invalid_layout);
       }
     return SKS_OK;
   }

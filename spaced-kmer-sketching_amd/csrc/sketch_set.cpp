@@ -165,13 +165,7 @@ int sks_sketch_set_export_csr(const sks_sketch_set* set, uint64_t* d_data, uint3
 
 int sks_sketch_set_info(const sks_sketch_set* set, sks_sketch_info* info) {
   if (!set || !info) return sks::fail(SKS_E_ARG, "sks_sketch_set_info: null argument");
-  info->window = set->window;
-  info->elem_words = set->elem_words;
-  info->mask[0] = set->mask[0];
-  info->mask[1] = set->mask[1];
-  info->policy = set->policy;
-  info->n = set->n;
-  info->has_names = set->names.empty() ? 0 : 1;
+  *info = info_of(*set);
   return SKS_OK;
 }
 
@@ -221,10 +215,7 @@ int sks_sketch_set_concat(sks_ctx* ctx, const sks_sketch_set* const* sets, uint3
   for (uint32_t i = 0; i < n_sets; ++i) {
     const sks_sketch_set* b = sets[i];
     if (!b) return sks::fail(SKS_E_ARG, "sks_sketch_set_concat: null set");
-    if (b->window != a->window || b->elem_words != a->elem_words || b->mask[0] != a->mask[0] ||
-        b->mask[1] != a->mask[1] || b->policy.kind != a->policy.kind ||
-        b->policy.param != a->policy.param || b->policy.nonce != a->policy.nonce ||
-        b->policy.flavour != a->policy.flavour)
+    if (set_differs_in(info_of(*a), info_of(*b), ParamRule::kAlways))
       return sks::fail(SKS_E_ARG, "sks_sketch_set_concat: sets differ in window, mask or policy");
     names = names && (b->names.size() == b->n);
   }

@@ -1,8 +1,10 @@
 // What the C-ABI translation units that run on a device share (ctx.cpp,
 // host_mem.cpp, sketch_set.cpp, kmer_list.cpp, build.cpp, build_post.cpp,
-// pairs.cpp, search_api.cpp, topk_api.cpp, cluster_api.cpp, gather_api.cpp, downsample_api.cpp, merge_api.cpp): the context, the sketch set
-// and k-mer list with the device blocks they own, the error macros, the
-// metadata arena and small argument helpers.
+// pairs.cpp, search_api.cpp, topk_api.cpp, cluster_api.cpp, gather_api.cpp,
+// downsample_api.cpp, merge_api.cpp): the context, the sketch set and k-mer
+// list with the device blocks they own, the error macros, the metadata arena,
+// SketchSpan and the group bounds of the set-level calls (their device-free
+// rules: set_rules.hpp) and small argument helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +29,7 @@
 #include "scan.hpp"
 #include "scratch_carve.hpp"
 #include "search_kernels.hpp"
+#include "set_rules.hpp"
 #include "sks.h"
 #include "sks_api_internal.hpp"
 #include "topk.hpp"
@@ -58,7 +61,7 @@ struct sks_ctx {
   sks::Scratch meta;                // small per-segment device arrays
   sks::Scratch iwork;               // intersection bucket tables
   sks::Scratch tdone;               // fused ANI: workgroups finished per join tile
-  sks::Scratch lay;                 // sks_all_pairs_ani: the join layout, its temp and packed counts
+  sks::Scratch lay;                 // one call's carve: sks_all_pairs_ani, the search walk, cluster, gather
   const uint32_t* layout_stat = nullptr;  // the last join-layout build's 2 status words (in iwork)
   std::vector<uint64_t> meta_host;  // staging for `meta`
   sks_timings last{};
@@ -197,6 +200,80 @@ int make_sketch_set(int device, int elem_words, int window, const uint64_t mask[
                     std::vector<uint32_t> sizes, std::vector<uint64_t> windows, std::vector<std::string> names,
                     const uint64_t* data_words, hipStream_t st, MetaUpload up, SetPtr* out);
 
+inline sks_sketch_info info_of(const sks_sketch_set& s) {
+  return {s.window, s.elem_words, {s.mask[0], s.mask[1]}, s.policy, s.n, s.names.empty() ? 0 : 1};
+}
+
+// ---- a set's arrays as the set-level calls take them ------------------------------------
+struct SketchSpan {
+  const uint64_t* data;
+  const uint64_t* starts;
+  const uint32_t* sizes;
+  uint32_t n, max_size;
+  uint64_t total;
+  const uint32_t* h_sizes;  // host copy of the sizes, or null (batches are then sized by max_size)
+};
+
+inline SketchSpan span_of(const sks_sketch_set* s) {
+  SketchSpan S{s->d_data(), s->d_starts(), s->d_sizes(), s->n, 0, 0, s->sizes.data()};
+  for (uint32_t v : s->sizes) {
+    S.max_size = std::max(S.max_size, v);
+    S.total += v;
+  }
+  return S;
+}
+
+// Element indices are 32-bit: "<who>: >= 2^32 elements <where>".
+inline int check_span_totals(const char* who, const char* where, uint64_t total_a, uint64_t total_b = 0) {
+  if (!((total_a | total_b) >> 32)) return SKS_OK;
+  return sks::fail(SKS_E_UNSUPPORTED, std::string(who) + ": >= 2^32 elements " + where);
+}
+
+// A query and a reference set that the search, top-k and gather may compare:
+// no differing field, both on the context's device, a mask that selects a
+// position.  `frac_only`: a refusal between the fields and the device, the text
+// after "<me>: " for sets that are not FracMinHash.  *info: the queries'.
+inline int search_sets_compatible(const sks_ctx* c, const std::string& me, const sks_sketch_set* queries,
+                                  const sks_sketch_set* refs, sks_sketch_info* info, int* kmer_num_ones,
+                                  const char* frac_only = nullptr) {
+  *info = info_of(*queries);
+  if (const char* field = set_differs_in(*info, info_of(*refs), ParamRule::kFracOnly))
+    return sks::fail(SKS_E_ARG, me + ": the query and reference sets differ in " + field);
+  if (frac_only && info->policy.kind != SKS_FRAC_MOD) return sks::fail(SKS_E_ARG, me + ": " + frac_only);
+  if (queries->device != c->device || refs->device != c->device)
+    return sks::fail(SKS_E_ARG, me + ": a set lives on another device than the context");
+  *kmer_num_ones = kmer_ones_of(info->mask);
+  if (*kmer_num_ones <= 0) return sks::fail(SKS_E_ARG, me + ": the sets' mask selects no position");
+  return SKS_OK;
+}
+
+// The group bounds the mask fixes for sketches of at most max_size elements
+// ((G + 1) * elem_words words for that size's log_b): no sampling pass.
+inline int mask_group_bounds(const uint64_t mask[2], int elem_words, uint32_t max_size, std::vector<uint64_t>* out) {
+  const uint32_t log_b = sks::join_log_b(std::max<uint32_t>(max_size, 1));
+  out->assign((size_t)(sks::join_layout_groups(log_b) + 1) * elem_words, 0);
+  return sks_join_layout_bounds_for_mask(mask, log_b, elem_words, out->data());
+}
+
+// Queues a layout's group bounds into d_bounds: the host's if given, else sampled from S.
+inline int queue_group_bounds(sks_ctx* c, const SketchSpan& S, uint32_t log_b, int ew,
+                              const std::vector<uint64_t>* h_bounds, uint64_t* d_bounds) {
+  if (h_bounds)
+    SKS_HIP(sks::pinned_h2d(d_bounds, h_bounds->data(), (size_t)(sks::join_layout_groups(log_b) + 1) * 8 * ew,
+                            c->stream));
+  else
+    SKS_HIP(sks::join_layout_bounds(S.data, S.starts, S.sizes, S.n, log_b, ew, d_bounds, c->stream));
+  return SKS_OK;
+}
+
+// A layout build raised status word 1 (*invalid_layout: for with_mask_bounds_retry).
+inline int fail_invalid_layout(const std::string& me, const std::string& what, const char* nothing,
+                               bool* invalid_layout) {
+  if (invalid_layout) *invalid_layout = true;
+  return sks::fail(SKS_E_UNSUPPORTED,
+                   me + ": the join layout of " + what + " could not be placed (invalid layout); " + nothing);
+}
+
 // ---- filters over a set's arrays (downsample_api.cpp) -----------------------------------
 // sks_sketch_set_downsample after its argument checks, over the CSR arrays
 // (d_data, d_starts, d_sizes; src_sizes on the host) of sketches made as `like`
@@ -205,6 +282,18 @@ int make_sketch_set(int device, int elem_words, int window, const uint64_t mask[
 int downsample_arrays(sks_ctx* c, const char* who, const uint64_t* d_data, const uint64_t* d_starts,
                       const uint32_t* d_sizes, const std::vector<uint32_t>& src_sizes, const sks_sketch_set& like,
                       uint64_t param, SetPtr* out);
+// The tail of a call whose count kernel decides the new sketches' sizes: kept
+// elements per kDownsampleChunk-element chunk in chunk_counts(c), reserved with
+// chunk_offs(c) before that kernel is queued.  size_set_from_counts queues
+// downsample_offsets (d_chunk_off: [set->n + 1] chunks before each sketch),
+// reads the sizes back (one wait), fails with "<who>: <too_large>" (SKS_E_HIP)
+// if sizes[g] > bound[g], and fills the set's host starts and sizes and
+// allocates its data to the exact total.  The caller's scatter follows.
+inline uint32_t* chunk_counts(sks_ctx* c) { return reinterpret_cast<uint32_t*>(c->flag.ptr); }
+inline uint64_t* chunk_offs(sks_ctx* c) { return reinterpret_cast<uint64_t*>(c->pos.ptr); }
+int reserve_chunk_counters(sks_ctx* c, uint64_t n_chunks);
+int size_set_from_counts(sks_ctx* c, const char* who, const char* too_large, uint64_t n_chunks,
+                         const uint64_t* d_chunk_off, const uint32_t* bound, sks_sketch_set* set);
 
 // ---- argument helpers (ctx.cpp) ---------------------------------------------------------
 // The opening checks of the entry points that take a join layout: a context, a

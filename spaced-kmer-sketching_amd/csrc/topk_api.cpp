@@ -35,13 +35,11 @@ int topk_check_k(const char* who, const TopkRule& t) {
   return SKS_OK;
 }
 
-// h_bounds: the host group bounds to use, or null to sample them once from the
-// references (as search_core).
-int topk_core(sks_ctx* c, const char* who, const SearchSide& Q, const SearchSide& R, int ew, int kmer_num_ones,
+// h_bounds, invalid_layout: as search_core.
+int topk_core(sks_ctx* c, const char* who, const SketchSpan& Q, const SketchSpan& R, int ew, int kmer_num_ones,
               const TopkRule& t, const std::vector<uint64_t>* h_bounds, sks_top_hit* d_hits, uint32_t* d_counts,
               bool* invalid_layout = nullptr) {
   const std::string me(who);
-  if (invalid_layout) *invalid_layout = false;
   if (Q.n == 0) return SKS_OK;
   DeviceGuard g(c->device);
   const size_t state_bytes = (size_t)Q.n * t.k * sizeof(TopkSlot);
@@ -89,10 +87,9 @@ int sks_search_topk(sks_ctx* c, const uint64_t* d_q_data, const uint64_t* d_q_st
   if ((q_n && (!d_q_starts || !d_q_sizes)) || (r_n && (!d_r_starts || !d_r_sizes)))
     return sks::fail(SKS_E_ARG, "sks_search_topk: null argument");
   SKS_TRY(topk_check_k("sks_search_topk", t));
-  if (q_total >= (1ull << 32) || r_total >= (1ull << 32))
-    return sks::fail(SKS_E_UNSUPPORTED, "sks_search_topk: >= 2^32 elements in one set");
-  const SearchSide Q{d_q_data, d_q_starts, d_q_sizes, q_n, q_max_size, q_total, nullptr};
-  const SearchSide R{d_r_data, d_r_starts, d_r_sizes, r_n, r_max_size, r_total, nullptr};
+  SKS_TRY(check_span_totals("sks_search_topk", "in one set", q_total, r_total));
+  const SketchSpan Q{d_q_data, d_q_starts, d_q_sizes, q_n, q_max_size, q_total, nullptr};
+  const SketchSpan R{d_r_data, d_r_starts, d_r_sizes, r_n, r_max_size, r_total, nullptr};
   return topk_core(c, "sks_search_topk", Q, R, elem_words, kmer_num_ones, t, nullptr, d_hits, d_counts);
 }
 
@@ -107,22 +104,16 @@ int sks_search_topk_sets(sks_ctx* c, const sks_sketch_set* queries, const sks_sk
   sks_sketch_info qi{};
   int ones = 0;
   SKS_TRY(search_sets_compatible(c, "sks_search_topk_sets", queries, refs, &qi, &ones));
-  const SearchSide Q = search_side_of(queries), R = search_side_of(refs);
-  if (Q.total >= (1ull << 32) || R.total >= (1ull << 32))
-    return sks::fail(SKS_E_UNSUPPORTED, "sks_search_topk_sets: >= 2^32 elements in one set");
+  const SketchSpan Q = span_of(queries), R = span_of(refs);
+  SKS_TRY(check_span_totals("sks_search_topk_sets", "in one set", Q.total, R.total));
   if (Q.n == 0 || R.n == 0)  // no layout to place
     return topk_core(c, "sks_search_topk_sets", Q, R, qi.elem_words, ones, t, nullptr, d_hits, d_counts);
-  // group bounds fixed by the mask: no sampling pass, the same for every batch
-  const uint32_t log_b = sks::join_log_b(std::max<uint32_t>(std::max(Q.max_size, R.max_size), 1));
-  std::vector<uint64_t> h_bounds((size_t)(sks::join_layout_groups(log_b) + 1) * qi.elem_words);
-  SKS_TRY(sks_join_layout_bounds_for_mask(qi.mask, log_b, qi.elem_words, h_bounds.data()));
-  bool invalid = false;
-  const int rc = topk_core(c, "sks_search_topk_sets", Q, R, qi.elem_words, ones, t, &h_bounds, d_hits, d_counts,
-                           &invalid);
-  if (!invalid) return rc;
-  // k-mers far from uniform overfilled a group of the mask's bounds: once more
-  // with bounds sampled from the references (SKS_E_UNSUPPORTED if that fails too)
-  return topk_core(c, "sks_search_topk_sets", Q, R, qi.elem_words, ones, t, nullptr, d_hits, d_counts);
+  // the mask's group bounds for every batch; sampled from the references if they cannot place a layout
+  std::vector<uint64_t> mask_bounds;
+  SKS_TRY(mask_group_bounds(qi.mask, qi.elem_words, std::max(Q.max_size, R.max_size), &mask_bounds));
+  return with_mask_bounds_retry(mask_bounds, [&](const std::vector<uint64_t>* h_bounds, bool* invalid) {
+    return topk_core(c, "sks_search_topk_sets", Q, R, qi.elem_words, ones, t, h_bounds, d_hits, d_counts, invalid);
+  });
 }
 
 }  // extern "C"
