@@ -26,7 +26,17 @@
 // kernel's lanes own 16 consecutive starts.)
 // Survivors (~1/c of windows) go to an LDS queue flushed with one global
 // atomic per flush, so the global counters see a few thousand atomics per
-// launch instead of one per survivor.
+// launch instead of one per survivor; a survivor that finds the queue full is
+// written directly, its slot taken with one global atomic per wave
+// (wave_aggregated_inc).  The pre-filter kernel first queues its candidates
+// (1 window in 2^min(s,4)) per wave: a passing lane takes its 16-byte slot with
+// a returning LDS atomic on the wave's cursor word, which holds the next free
+// slot's LDS address; a scalar count follows the cursor and the list is
+// finished 64 candidates at a time.
+// This unit is compiled without LLVM's AMDGPU atomic optimizer (Makefile), so
+// every atomicAdd below is the instruction it names, per active lane: an
+// atomic that should be one per wave is issued by one lane or aggregated in
+// source.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -168,6 +178,27 @@ __device__ __forceinline__ uint32_t rev_pairs(uint32_t x) {
 }
 
 
+// atomicAdd(counter, 1) from every active lane of the wave as ONE atomic: the
+// lowest active lane adds their number, its return is broadcast and each lane
+// adds its rank among the active ones (the slots a per-lane atomic would have
+// handed out, in lane order).  `counter` must be wave-uniform.  Call it inside
+// the divergent branch: the ballot of `true` is that branch's lane mask.  The
+// compiler's atomic optimizer does this by itself; this unit is built without
+// it, and 64 atomics per wave on one word would meet the ~88 per microsecond
+// one counter word takes (MI355X_MICROARCH.md "dequeue").  (Here and not in
+// wave_prims.hpp: the scan does not include the join's primitives.)
+__device__ __forceinline__ unsigned long long wave_aggregated_inc(unsigned long long* counter) {
+  const uint64_t act = __ballot(true);
+  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32),
+                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
+  unsigned long long base = 0;
+  if (rank == 0) base = atomicAdd(counter, (unsigned long long)__popcll(act));
+  // readfirstlane reads the lowest active lane: the one that did the add
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
+  return (((unsigned long long)hi << 32) | lo) + rank;
+}
+
 template <int MODE>
 struct Queue {
   uint64_t key[qcap<MODE>()];
@@ -184,8 +215,8 @@ __device__ __forceinline__ void emit(const ScanParams& p, Queue<MODE>& q, uint32
   if (slot < (uint32_t)qcap<MODE>()) {
     q.key[slot] = key;
     if constexpr (MODE == kModeBottom) q.val[slot] = val;
-  } else {  // queue full: rare direct path
-    unsigned long long g = atomicAdd(&p.seg_count[seg], 1ull);
+  } else {  // queue full: the direct path, one global atomic per wave
+    unsigned long long g = wave_aggregated_inc(&p.seg_count[seg]);
     if (g < p.seg_out_cap[seg]) {
       uint64_t o = p.seg_out_off[seg] + g;
       p.out_key[o] = key;
@@ -296,6 +327,8 @@ __global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(
   __shared__ Queue<MODE> q;
   // (z, c) of windows past the low-bits pre-filter, per wave (PRE only)
   __shared__ ulonglong2 s_cand[PRE ? (kBlock / 64) * kCandCap : 1];
+  // per wave: the cursor, the LDS byte address of its list's next free slot (PRE only)
+  __shared__ uint32_t s_ctop[PRE ? kBlock / 64 : 1];
 
   __shared__ unsigned long long s_next;  // dynamic tiles: the next chunk's first tile
 
@@ -526,15 +559,40 @@ __global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(
       // min(s, 4) bits of its fmh are zero, and those follow from the low 32
       // bits of the last multiply. Windows passing that test (1/8 for c = 1000)
       // are queued per wave in LDS and finished 64 at a time, all lanes busy.
-      // the wave's candidate buffer, wave-uniform: readfirstlane keeps it in an
-      // SGPR so a candidate's LDS address is one v_lshl_add_u32 of its rank
-      ulonglong2* cb = s_cand + __builtin_amdgcn_readfirstlane(tid >> 6) * kCandCap;
+      // A passing lane takes its slot from the wave's cursor with a returning
+      // LDS atomic (ds_add_rtn_u32: the LDS unit hands the passing lanes
+      // distinct consecutive slots, in no particular order — the sketch is a
+      // sorted set), so the append costs no ballot rank (2 v_mbcnt) and no slot
+      // arithmetic.  This needs the unit built without the compiler's atomic
+      // optimizer (Makefile), which would turn the atomic back into exactly that.
+      // The cursor holds the slot's LDS byte address itself (the list's base plus
+      // 16 per candidate), so the atomic's return is the ds_write's address.
+      // the wave's candidate buffer, wave-uniform: readfirstlane keeps it in SGPRs
+      const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+      ulonglong2* cb = s_cand + wv * kCandCap;
+      uint32_t* const ctop = s_ctop + wv;
+      typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+      typedef __attribute__((address_space(3))) u64x2 lds_u64x2;
+      const uint32_t cb_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)cb;
+      // The cursor is written (reset) by lane 0 and added to by the passing
+      // lanes of the same wave.  A wave's LDS instructions are issued and
+      // executed in program order, so all that is needed is that the compiler
+      // keeps that order: the store and the atomic name the same word, and the
+      // wavefront-scope fences around the wave barrier (no instructions) make
+      // the hand-over between lanes an ordering the memory model knows.
+      auto set_cursor = [&](uint32_t n) {  // the list holds n candidates
+        if (lane == 0) *ctop = cb_lds + 16 * n;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      };
       const uint32_t pmask = p.low_mask & 0xFu;
       const uint32_t kbits = (uint32_t)p.kconst & pmask;
       // low bits of c = 2^s * d the pre-filter has not tested (none when s <= 4):
       // a finished candidate needs only d | fmh then
       const uint32_t rest_lo = p.low_mask & ~0xFu, rest_hi = p.high_mask;
-      uint32_t cnt = 0;  // wave-uniform
+      uint32_t cnt = 0;  // wave-uniform: candidates in the list (the cursor's count, kept scalar)
+      set_cursor(0);
       auto finish = [&](uint32_t n) {  // candidates [0, n), n <= 64
         __builtin_amdgcn_wave_barrier();
         if ((uint32_t)lane < n) {
@@ -553,10 +611,17 @@ __global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(
           const uint64_t z = mix3_head(c);
           const uint32_t ylo = (uint32_t)z * (uint32_t)kMixMul;
           const bool pass = (((ylo ^ (ylo >> 28)) & pmask) == kbits) && valid;
+          // the ballot feeds the scalar count only (taken next to the compare: after
+          // the branch the compiler would rebuild the mask with a select and a compare)
           const uint64_t bal = __ballot(pass);
-          const uint32_t below = __builtin_amdgcn_mbcnt_hi(
-              (uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-          if (pass) cb[cnt + below] = make_ulonglong2(z, c);
+          if (pass) {
+            // cnt < 64 before the window and at most 64 lanes pass: slots < kCandCap
+            const uint32_t slot = atomicAdd(ctop, 16u);
+            u64x2 zc;
+            zc.x = z;
+            zc.y = c;
+            *(lds_u64x2*)(uintptr_t)slot = zc;
+          }
           cnt += (uint32_t)__popcll(bal);
           if (cnt >= 64) {
             finish(64);
@@ -566,6 +631,7 @@ __global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(
             __builtin_amdgcn_wave_barrier();
             if ((uint32_t)lane < rest) cb[lane] = t;
             cnt = rest;
+            set_cursor(rest);
           }
       };
       if (wave_clean) {
@@ -785,7 +851,7 @@ __global__ __launch_bounds__(kBlock) void scan_kernel_wide(ScanParams p) {
         if (slot < cap) {
           q_a[slot] = a; q_b[slot] = b; q_c[slot] = ch;
         } else {
-          unsigned long long gi = atomicAdd(&p.seg_count[g.seg], 1ull);
+          unsigned long long gi = wave_aggregated_inc(&p.seg_count[g.seg]);
           if (gi < p.seg_out_cap[g.seg]) {
             uint64_t o = p.seg_out_off[g.seg] + gi;
             p.out_key[o] = a;

@@ -2,6 +2,7 @@
 # Build libsks.so with extra compile definitions into variants/libsks_<tag>.so
 # (for A/B runs through SKS_LIB=...; *.so stays out of git but ships to the box).
 #   bash tools/build_variant.sh slots1024 -DSKS_JOIN_LOG_SLOTS=10
+# Built through the package Makefile, so scan.hip keeps its per-unit flag (SCAN_ATOMICS).
 set -e
 TAG=$1; shift
 R=$(cd "$(dirname "$0")/.." && pwd)

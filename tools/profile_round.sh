@@ -10,6 +10,8 @@
 #    two SQ groups for the scan kernel.
 # 3. SQ groups over tools/bench_pairs.py (config 4): k_join, k_bottom_fused.
 # 4. tools/summarize_round.py -> gpurun_out/round_<tag>/summary (copy to profiles/<tag>).
+# SCAN_ONLY=1 (a round that changes only the scan): the trace runs the config-3 part
+# alone and step 3 is skipped; the summary then holds the scan's files only.
 set -e
 TAG=$1
 STEPS=${STEPS:-20}; WARMUP=${WARMUP:-2}
@@ -19,7 +21,9 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 ARGS="$R/bench.py --full --steps $STEPS --warmup $WARMUP"
 C3="--no-pairs --no-sweep --no-e2e --no-c3-sharded --no-c2 --no-cpu-baseline"
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 $ARGS > $OUT/bench_traced.json 2> $OUT/trace.log
+TRACED=$ARGS
+[ -n "$SCAN_ONLY" ] && TRACED="$ARGS $C3"
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 $TRACED > $OUT/bench_traced.json 2> $OUT/trace.log
 echo "trace done"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- python3 $ARGS $C3 > $OUT/fetch.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o run -- python3 $ARGS $C3 > $OUT/write.log 2>&1
@@ -27,6 +31,7 @@ echo "traffic done"
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU --output-format csv -d $OUT/sq/p1 -o run -- python3 $ARGS $C3 > $OUT/sq1.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE --output-format csv -d $OUT/sq/p2 -o run -- python3 $ARGS $C3 > $OUT/sq2.log 2>&1
 echo "scan counters done"
+if [ -z "$SCAN_ONLY" ]; then
 SKS_BENCH_KERNELS=join timeout -k 10 200 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU --output-format csv -d $OUT/pairs/p1 -o run -- python3 $R/tools/bench_pairs.py 1000 2 > $OUT/pairs1.log 2>&1
 SKS_BENCH_KERNELS=join timeout -k 10 200 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE --output-format csv -d $OUT/pairs/p2 -o run -- python3 $R/tools/bench_pairs.py 1000 2 > $OUT/pairs2.log 2>&1
 SKS_BENCH_KERNELS=join timeout -k 10 200 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU --output-format csv -d $OUT/pairs_wide/p1 -o run -- python3 $R/tools/bench_pairs.py 1000 2 family 45 > $OUT/pairsw1.log 2>&1
@@ -36,5 +41,6 @@ SKS_BENCH_KERNELS=join timeout -k 10 200 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ
 SKS_BENCH_KERNELS=join timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pairs_mem/p1 -o run -- python3 $R/tools/bench_pairs.py 1000 2 > $OUT/pairsm1.log 2>&1
 SKS_BENCH_KERNELS=join timeout -k 10 200 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/pairs_mem/p2 -o run -- python3 $R/tools/bench_pairs.py 1000 2 > $OUT/pairsm2.log 2>&1
 echo "pair counters done"
+fi
 python3 $R/tools/summarize_round.py $OUT $OUT/summary $WARMUP $STEPS
 echo profile done

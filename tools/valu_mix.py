@@ -63,6 +63,8 @@ def main(dst=None):
     rates = measured_rates()
     with tempfile.TemporaryDirectory() as td:
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
+                        # the Makefile's per-unit flag of scan.hip (SCAN_ATOMICS)
+                        "-mllvm", "-amdgpu-atomic-optimizer-strategy=None",
                         "-I", os.path.join(ROOT, "include"), "-save-temps", "-c",
                         os.path.join(PKG, "csrc", "scan.hip"), "-o", os.path.join(td, "scan.o")],
                        cwd=td, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
