@@ -33,6 +33,8 @@
 // a returning LDS atomic on the wave's cursor word, which holds the next free
 // slot's LDS address; a scalar count follows the cursor and the list is
 // finished 64 candidates at a time.
+// For w <= 31 the canonical minimum of the narrow FracMinHash and bottom-s
+// kernels is one v_min_f64 on the bit patterns (min_below_2_62).
 // This unit is compiled without LLVM's AMDGPU atomic optimizer (Makefile), so
 // every atomicAdd below is the instruction it names, per active lane: an
 // atomic that should be one per wave is issued by one lane or aggregated in
@@ -318,7 +320,24 @@ constexpr int min_waves() {
 
 constexpr uint32_t kCandCap = 128;  // pre-filter candidates per wave (< 64 + 64)
 
-template <int MODE, int FLAVOUR, int PRE = 0>
+// Unsigned minimum of two values below 2^62 in one VALU op.  Read as IEEE
+// doubles such bit patterns are non-negative and finite (bit 62 clear: the
+// exponent field is never all ones, so no NaN and no infinity), and finite
+// non-negative doubles order exactly as their bit patterns do; zero and the
+// denormal patterns (values below 2^52) included, since the kernels keep f64
+// denormals (the compiler's default float mode) and a minimum returns one of
+// its operands unchanged.  The masked windows of w <= 31 use at most 62 bits.
+// The builtin fmin would add a canonicalising v_max_f64 per operand, hence the asm.
+constexpr int kFminMaxW = 31;
+__device__ __forceinline__ uint64_t min_below_2_62(uint64_t a, uint64_t b) {
+  uint64_t r;
+  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+// FMIN: the canonical minimum is min_below_2_62 (launch_scan picks it for
+// w <= kFminMaxW); otherwise the 64-bit compare and select, which w = 32 needs.
+template <int MODE, int FLAVOUR, int PRE = 0, int FMIN = 0>
 __global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(ScanParams p) {
   __shared__ uint32_t s_raw[kLoadVecs * 4];
   __shared__ uint32_t s_be[kWords + 2 + kBeOff];
@@ -482,7 +501,8 @@ __global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(
       const uint64_t F = (((uint64_t)fh) << 32) | fl;
       const uint64_t R = (((uint64_t)rh) << 32) | rl;
       const uint64_t fm = F & p.mask_lo, rm = R & p.mask_lo;
-      return fm < rm ? fm : rm;
+      if constexpr (FMIN) return min_below_2_62(fm, rm);
+      else return fm < rm ? fm : rm;
     };
     // canonical masked k-mer of window m, re-read from LDS (run-time m: the
     // survivors of the keep-mask loop)
@@ -872,6 +892,13 @@ __global__ __launch_bounds__(kBlock) void scan_kernel_wide(ScanParams p) {
   wflush(count_seg);
 }
 
+// The narrow FracMinHash and bottom-s kernels in the instantiation their window
+// length allows: the one-op canonical minimum for w <= kFminMaxW.
+template <int MODE, int FLAVOUR, int PRE, class Run>
+hipError_t run_narrow(const ScanParams& p, Run run) {
+  return p.w <= kFminMaxW ? run(scan_kernel<MODE, FLAVOUR, PRE, 1>) : run(scan_kernel<MODE, FLAVOUR, PRE, 0>);
+}
+
 constexpr int kGridOversubscribe = 16;
 constexpr int kDynOversubscribe = 2;
 
@@ -930,20 +957,20 @@ hipError_t launch_scan(const ScanParams& p, int mode, int flavour, bool wide, in
   if (!wide && p.tile_queue) {
     if (mode == kModeFrac) {
       static const bool no_pre = getenv("SKS_NO_PREFILTER") != nullptr;
-      if (flavour == 0 && (p.low_mask & 0xFu) && !no_pre) return pick_dyn(scan_kernel<kModeFrac, 0, 1>);
-      return flavour == 0 ? pick_dyn(scan_kernel<kModeFrac, 0>) : pick_dyn(scan_kernel<kModeFrac, 1>);
+      if (flavour == 0 && (p.low_mask & 0xFu) && !no_pre) return run_narrow<kModeFrac, 0, 1>(p, pick_dyn);
+      return flavour == 0 ? run_narrow<kModeFrac, 0, 0>(p, pick_dyn) : run_narrow<kModeFrac, 1, 0>(p, pick_dyn);
     }
     if (mode == kModeBottom)
-      return flavour == 0 ? pick_dyn(scan_kernel<kModeBottom, 0>) : pick_dyn(scan_kernel<kModeBottom, 1>);
+      return flavour == 0 ? run_narrow<kModeBottom, 0, 0>(p, pick_dyn) : run_narrow<kModeBottom, 1, 0>(p, pick_dyn);
   }
   if (!wide) {
     if (mode == kModeFrac) {
       static const bool no_pre = getenv("SKS_NO_PREFILTER") != nullptr;
-      if (flavour == 0 && (p.low_mask & 0xFu) && !no_pre) return pick(scan_kernel<kModeFrac, 0, 1>);
-      return flavour == 0 ? pick(scan_kernel<kModeFrac, 0>) : pick(scan_kernel<kModeFrac, 1>);
+      if (flavour == 0 && (p.low_mask & 0xFu) && !no_pre) return run_narrow<kModeFrac, 0, 1>(p, pick);
+      return flavour == 0 ? run_narrow<kModeFrac, 0, 0>(p, pick) : run_narrow<kModeFrac, 1, 0>(p, pick);
     }
     if (mode == kModeList) return flavour == 0 ? pick(scan_kernel<kModeList, 0>) : pick(scan_kernel<kModeList, 1>);
-    return flavour == 0 ? pick(scan_kernel<kModeBottom, 0>) : pick(scan_kernel<kModeBottom, 1>);
+    return flavour == 0 ? run_narrow<kModeBottom, 0, 0>(p, pick) : run_narrow<kModeBottom, 1, 0>(p, pick);
   }
   if (mode == kModeFrac) return flavour == 0 ? pick(scan_kernel_wide<kModeFrac, 0>) : pick(scan_kernel_wide<kModeFrac, 1>);
   if (mode == kModeList) return flavour == 0 ? pick(scan_kernel_wide<kModeList, 0>) : pick(scan_kernel_wide<kModeList, 1>);

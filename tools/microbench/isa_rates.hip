@@ -46,7 +46,9 @@ __global__ __launch_bounds__(256) void k(uint32_t* out, uint32_t seed) {
   if constexpr (OP == 18) asm volatile("v_perm_b32 %0, %0, %1, %1" : "+v"(r[i]) : "v"(s));       \
   if constexpr (OP == 19) asm volatile("v_bfe_u32 %0, %0, 3, 9" : "+v"(r[i]));                   \
   if constexpr (OP == 20) asm volatile("v_or3_b32 %0, %0, %1, %1" : "+v"(r[i]) : "v"(s));       \
-  if constexpr (OP == 21) asm volatile("v_lshl_or_b32 %0, %0, 3, %1" : "+v"(r[i]) : "v"(s));
+  if constexpr (OP == 21) asm volatile("v_lshl_or_b32 %0, %0, 3, %1" : "+v"(r[i]) : "v"(s));          \
+  if constexpr (OP == 22) asm volatile("v_min_f64 %0, %0, %1" : "+v"(*(uint64_t*)&r[i & ~1]) : "v"(*(uint64_t*)&h[i & ~1])); \
+  if constexpr (OP == 23) asm volatile("v_cmp_lt_f64 vcc, %0, %1" :: "v"(*(uint64_t*)&r[i & ~1]), "v"(*(uint64_t*)&h[i & ~1]) : "vcc");
       REP8(B)
 #undef B
     }
@@ -127,8 +129,8 @@ int main() {
                          "v_lshrrev_b64", "v_alignbit_b32", "v_mad_u32_u24", "v_and_b32",
                          "v_add_u32", "v_lshlrev_b32", "v_mov_b32", "v_cndmask_b32",
                          "v_cmp_lt_u64", "v_xor_b32_e64", "v_perm_b32", "v_bfe_u32", "v_or3_b32",
-                         "v_lshl_or_b32"};
-  constexpr int NOPS = 22;
+                         "v_lshl_or_b32", "v_min_f64", "v_cmp_lt_f64"};
+  constexpr int NOPS = 24;
   float t[NOPS];
   t[0] = time_kernel(k<0>, blocks, out, 3u);
   t[1] = time_kernel(k<1>, blocks, out, 3u);
@@ -152,6 +154,8 @@ int main() {
   t[19] = time_kernel(k<19>, blocks, out, 3u);
   t[20] = time_kernel(k<20>, blocks, out, 3u);
   t[21] = time_kernel(k<21>, blocks, out, 3u);
+  t[22] = time_kernel(k<22>, blocks, out, 3u);
+  t[23] = time_kernel(k<23>, blocks, out, 3u);
   const double simds = p.multiProcessorCount * 4.0;
   for (int i = 0; i < NOPS; ++i) {
     double per_simd = insts / simds;  // wave-instructions per SIMD

@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
                                 "spaced-kmer-sketching_amd"))
 import srchash  # noqa: E402
 
-SCAN = "scan_kernel<0, 0, 1>"  # FracMinHash, flavour B, low-bits pre-filter (config 3)
+SCAN = "scan_kernel<0, 0, 1, 1>"  # FracMinHash, flavour B, low-bits pre-filter, w <= 31 (config 3)
 
 
 def _one(d, pattern):

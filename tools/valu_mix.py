@@ -2,11 +2,12 @@
 bench line's roofline.valu).
 
 Compiles csrc/scan.hip for gfx950 with -save-temps (the Makefile's flags) in a
-temp dir, takes the scan_kernel<0, 0, 1> function (FracMinHash, flavour B,
-low-bits pre-filter: config 3), splits it into basic blocks and picks the
+temp dir, takes the scan_kernel<0, 0, 1, 1> function (FracMinHash, flavour B,
+low-bits pre-filter, one-op canonical minimum: config 3), splits it into basic blocks and picks the
 steady-state block of the clean-wave window loop (one window per lane per
 block): the leanest of the blocks holding the hash's ten v_mad_u64_u32.  Each VALU op is priced with the measured wave64 issue
-cost per SIMD of profiles/r01/isa_rates_microbench.txt (cycles at 2.4 GHz):
+cost per SIMD of profiles/r01/isa_rates_microbench.txt (cycles at 2.4 GHz; ops
+measured later, v_min_f64 among them, from profiles/r10/isa_rates_microbench.txt):
 ops measured there take their own figure; an unmeasured op takes the figure
 of its encoding class (VOP3 / 64-bit / multiply ~4.2, VOP2 / VOP1 ~2.2).
 Writes JSON: the hot block's VALU count, cycles, mean cycles per VALU, the
@@ -25,16 +26,19 @@ PKG = os.path.join(ROOT, "spaced-kmer-sketching_amd")
 sys.path.insert(0, PKG)
 import srchash  # noqa: E402
 
-KERNEL = "_ZN3sks12_GLOBAL__N_111scan_kernelILi0ELi0ELi1EEEvNS_10ScanParamsE"
+KERNEL = "_ZN3sks12_GLOBAL__N_111scan_kernelILi0ELi0ELi1ELi1EEEvNS_10ScanParamsE"
 RATES = os.path.join(ROOT, "profiles", "r01", "isa_rates_microbench.txt")
+# ops added to the microbenchmark later (v_min_f64, v_cmp_lt_f64); r01's figure wins where both have one
+RATES_LATER = os.path.join(ROOT, "profiles", "r10", "isa_rates_microbench.txt")
 
 
 def measured_rates():
     out = {}
-    for line in open(RATES):
-        m = re.match(r"(v_\w+)\s+[\d.]+ ms.*cycles@2\.4GHz=([\d.]+)\)", line)
-        if m:
-            out[m.group(1)] = float(m.group(2))
+    for path in (RATES, RATES_LATER):
+        for line in open(path):
+            m = re.match(r"(v_\w+)\s+[\d.]+ ms.*cycles@2\.4GHz=([\d.]+)\)", line)
+            if m:
+                out.setdefault(m.group(1), float(m.group(2)))
     return out
 
 
@@ -102,7 +106,7 @@ def main(dst=None):
         cycles += c
         e = table.setdefault(op, {"count": 0, "cycles_each": c, "priced_by": how})
         e["count"] += 1
-    out = {"kernel": "scan_kernel<0, 0, 1>", "hot_block_valu": len(hot), "hot_block_cycles": cycles,
+    out = {"kernel": "scan_kernel<0, 0, 1, 1>", "hot_block_valu": len(hot), "hot_block_cycles": cycles,
            "mean_cycles_per_valu": cycles / len(hot),
            "cycles_unit": "wave64 issue cycles per SIMD (profiles/r01/isa_rates_microbench.txt, 2.4 GHz)",
            "windows_per_hot_block_iteration_per_lane": 1,
