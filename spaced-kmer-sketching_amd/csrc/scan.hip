@@ -23,7 +23,10 @@
 // 16 (16 g + m) + r, m = 0..15: 16 bases apart, so consecutive windows of a
 // lane share a 32-bit word of F and of R and each window costs one new funnel
 // shift (v_alignbit_b32) per strand, by a per-lane constant amount.  (The wide
-// kernel's lanes own 16 consecutive starts.)
+// kernel's lanes own 16 consecutive starts.)  The narrow kernel keeps its segment
+// cursor and the segment's geometry in scalar registers (SegCursor), read from
+// memory only when the cursor moves, and prefetches a tile that lies whole
+// inside its segment from a scalar base plus the lane's constant offset.
 // Survivors (~1/c of windows) go to an LDS queue flushed with one global
 // atomic per flush, so the global counters see a few thousand atomics per
 // launch instead of one per survivor; a survivor that finds the queue full is
@@ -87,14 +90,110 @@ __device__ __forceinline__ Geom tile_geom(const ScanParams& p, uint64_t tile, ui
   return g;
 }
 
+// A value every lane of the wave holds alike, moved to the scalar registers:
+// what is computed from it (tile geometry, 64-bit compares, a load's base) then
+// runs on the scalar unit, once per wave.
+// (The builtin returns int: each half goes through uint32_t, or widening the
+// low one would sign-extend bit 31 over the high one.)
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// A wave-uniform 64-bit value given a scalar register pair of its own (no
+// instruction beyond a possible copy).  The compiler then neither spills it as
+// part of the block of kernel arguments it arrived in (a spilled SGPR costs a
+// v_readlane, a VALU op, at every use) nor folds it into per-lane address
+// arithmetic: a load from such a base plus a 32-bit lane offset takes the
+// SGPR-base form of global_load.
+__device__ __forceinline__ uint64_t own_sgprs(uint64_t v) {
+  asm("" : "+s"(v));
+  return v;
+}
+
+// a < b for wave-uniform 64-bit values, on the scalar unit, as the borrow of
+// a - b.  The scalar unit has no ordered 64-bit compare: the compiler moves one
+// side to VGPRs for a v_cmp (two VALU ops per wave and test), also when the
+// source asks for the borrow.
+__device__ __forceinline__ bool uniform_less(uint64_t a, uint64_t b) {
+  uint32_t diff, borrow;
+  asm("s_sub_u32 %0, %2, %4\n\ts_subb_u32 %0, %3, %5\n\ts_cselect_b32 %1, 1, 0"
+      : "=&s"(diff), "=s"(borrow)
+      : "s"((uint32_t)a), "s"((uint32_t)(a >> 32)), "s"((uint32_t)b), "s"((uint32_t)(b >> 32))
+      : "scc");
+  return borrow != 0;
+}
+
+// The narrow kernel's segment cursor with the segment's geometry beside it, all
+// wave-uniform (SGPRs).  The arrays are read when the cursor moves (and once at
+// the start), not per tile: the kernel also stores to global memory, so the
+// compiler cannot hoist such loads itself and each one costs a vector load, a
+// full wait and 64-bit per-lane arithmetic behind it.
+template <int MODE>
+struct SegCursor {
+  uint32_t seg;
+  uint64_t next_prefix;  // tile_prefix[seg + 1]: the first tile past the segment
+  uint64_t win_off;      // seg_begin[seg] - kTile * tile_prefix[seg]: win0 = win_off + kTile * tile
+  int64_t end;           // seg_end[seg]
+  uint64_t thresh;       // seg_thresh[seg] (bottom-s only)
+
+  // the segment's own figures; prefix = tile_prefix[seg]
+  __device__ __forceinline__ void load(const ScanParams& p, uint64_t prefix) {
+    win_off = uniform64(p.seg_begin[seg]) - prefix * (uint64_t)kTile;
+    end = (int64_t)uniform64(p.seg_end[seg]);
+    if constexpr (MODE == kModeBottom) thresh = uniform64(p.seg_thresh[seg]);
+  }
+  __device__ __forceinline__ void start(const ScanParams& p, uint32_t s) {
+    seg = __builtin_amdgcn_readfirstlane(s);
+    next_prefix = uniform64(p.tile_prefix[seg + 1]);
+    load(p, uniform64(p.tile_prefix[seg]));
+  }
+  // advance until `tile` is inside the segment (tile_geom's walk: tiles only grow)
+  __device__ __forceinline__ void seek(const ScanParams& p, uint64_t tile) {
+    if (seg + 1 < p.n_seg && !uniform_less(tile, next_prefix)) {
+      uint64_t prefix;
+      do {  // segments without a tile are stepped over reading their prefix alone
+        ++seg;
+        prefix = next_prefix;
+        next_prefix = uniform64(p.tile_prefix[seg + 1]);
+      } while (seg + 1 < p.n_seg && !uniform_less(tile, next_prefix));
+      load(p, prefix);
+    }
+  }
+};
+
+// What the window phase needs of a tile, fixed when the tile is prefetched
+// (wave-uniform).
+struct TileGeom {
+  uint64_t win0;    // byte index of the tile's first window start
+  uint64_t thresh;  // bottom-s: the segment's threshold
+  uint32_t seg;
+  uint32_t shift;   // align_shift of win0
+};
+
+// The sequence as a pointer that names the global address space: a pointer
+// rebuilt from own_sgprs' integer would otherwise be a generic one (flat loads).
+typedef const __attribute__((address_space(1))) uint8_t* GlobalBytes;
+__device__ __forceinline__ GlobalBytes global_bytes(uint64_t address) {
+  return reinterpret_cast<GlobalBytes>((uintptr_t)address);
+}
+
+__device__ __forceinline__ uint4 load16(const uint8_t* at) { return *reinterpret_cast<const uint4*>(at); }
+__device__ __forceinline__ uint4 load16(GlobalBytes at) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 v = *reinterpret_cast<const __attribute__((address_space(1))) u32x4*>(at);
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+
 // Load the 16-B vector #k of a tile: bytes [base + 16k, base + 16k + 16) where
 // `base` (relative to seq, possibly negative) is 16-B aligned in absolute
 // address terms, so every vector load is aligned even when the caller's
 // sequence pointer is not.  Bytes at or past seg_end read as a separator.
-__device__ __forceinline__ uint4 load_vec(const uint8_t* __restrict__ seq, int64_t base, int k,
-                                          int64_t seg_end) {
+template <class Bytes>
+__device__ __forceinline__ uint4 load_vec(Bytes seq, int64_t base, int k, int64_t seg_end) {
   int64_t a = base + 16 * (int64_t)k;
-  if (a + 16 <= seg_end) return *reinterpret_cast<const uint4*>(seq + a);
+  if (a + 16 <= seg_end) return load16(seq + a);
   uint32_t wv[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -111,8 +210,9 @@ __device__ __forceinline__ uint4 load_vec(const uint8_t* __restrict__ seq, int64
 }
 
 // Offset of win0 inside its absolutely aligned 16-B chunk.
-__device__ __forceinline__ uint32_t align_shift(const uint8_t* seq, uint64_t win0) {
-  return (uint32_t)(((uintptr_t)seq + win0) & 15u);
+template <class Bytes>
+__device__ __forceinline__ uint32_t align_shift(Bytes seq, uint64_t win0) {
+  return (uint32_t)(((uint64_t)(uintptr_t)seq + win0) & 15u);
 }
 
 // 4 ASCII bytes -> 8 bits of little-endian 2-bit codes + 4 invalid bits.
@@ -307,14 +407,16 @@ constexpr int kBeOff = 2;  // s_be[kBeOff + i] = word i; two zero words in front
 // Waves per SIMD the compiler must leave room for (its register budget is
 // 512 / waves): 7 for the pre-filter kernel (what its ~100 SGPRs allow, and
 // what the runtime's occupancy query answers), 4 for list mode with its large
-// queue, 5 for the rest.  Without it the compiler spends registers on hoisted
-// addresses and a whole wave per SIMD goes.
-template <int MODE, int PRE>
+// queue, 6 for bottom-s with the one-op minimum (79 VGPRs when left alone in
+// round 10; asked for since round 11, whose scalar tile geometry otherwise
+// tempts the compiler to 85), 5 for the rest.  Without it the compiler spends
+// registers on hoisted addresses and a whole wave per SIMD goes.
+template <int MODE, int PRE, int FMIN>
 constexpr int min_waves() {
 #ifdef SKS_SCAN_MIN_WAVES
   return SKS_SCAN_MIN_WAVES;
 #else
-  return PRE ? 7 : MODE == kModeList ? 4 : 5;
+  return PRE ? 7 : MODE == kModeList ? 4 : (MODE == kModeBottom && FMIN) ? 6 : 5;
 #endif
 }
 
@@ -338,7 +440,7 @@ __device__ __forceinline__ uint64_t min_below_2_62(uint64_t a, uint64_t b) {
 // FMIN: the canonical minimum is min_below_2_62 (launch_scan picks it for
 // w <= kFminMaxW); otherwise the 64-bit compare and select, which w = 32 needs.
 template <int MODE, int FLAVOUR, int PRE = 0, int FMIN = 0>
-__global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(ScanParams p) {
+__global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE, FMIN>())) void scan_kernel(ScanParams p) {
   __shared__ uint32_t s_raw[kLoadVecs * 4];
   __shared__ uint32_t s_be[kWords + 2 + kBeOff];
   __shared__ uint32_t s_lc[kWords + 2];
@@ -406,30 +508,77 @@ __global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(
     uint32_t mid = (seg_lo + seg_hi) >> 1;
     if (p.tile_prefix[mid] <= t_begin) seg_lo = mid; else seg_hi = mid;
   }
-  uint32_t cur_seg = seg_lo, pf_seg = seg_lo;
-
-  // prefetch the first tile
-  Geom pg = tile_geom(p, t_begin, pf_seg);
-  int64_t pf_base = (int64_t)pg.win0 - align_shift(p.seq, pg.win0);
-  uint4 v0 = load_vec(p.seq, pf_base, tid, (int64_t)pg.seg_end);
-  uint4 v1 = make_uint4(0, 0, 0, 0);
-  if (tid < kLoadVecs - kBlock) v1 = load_vec(p.seq, pf_base, kBlock + tid, (int64_t)pg.seg_end);
+  // The one segment cursor follows the prefetch: a tile's geometry is fixed
+  // when its bytes are requested (pg) and handed to the tile's own iteration,
+  // since the tile prefetched is always the next one processed.
+  SegCursor<MODE> sc;
+  sc.start(p, seg_lo);
+  const GlobalBytes seq = global_bytes(own_sgprs((uint64_t)(uintptr_t)p.seq));
+  TileGeom pg;
+  uint4 v0, v1 = make_uint4(0, 0, 0, 0);
+  // Tile t's geometry on the scalar unit, and its kLoadVecs 16-byte vectors
+  // from the aligned base at or below its first window.  An interior tile — the
+  // last vector ends inside the segment, a wave-uniform test — loads from that
+  // scalar base plus the lane's constant offset; only a segment's last tile(s)
+  // take load_vec's per-lane bounds and its byte-wise masked tail.  Both read
+  // exactly the vectors that lie whole inside [.., seg_end).
+  auto prefetch = [&](uint64_t t) {
+    sc.seek(p, t);
+    pg.seg = sc.seg;
+    pg.thresh = (MODE == kModeBottom) ? sc.thresh : 0;
+    pg.win0 = sc.win_off + t * (uint64_t)kTile;
+    pg.shift = align_shift(seq, pg.win0);
+    const int64_t base = (int64_t)pg.win0 - pg.shift;
+    // (both sides are non-negative: base >= -15)
+    const bool interior = !uniform_less((uint64_t)sc.end, (uint64_t)(base + 16 * kLoadVecs));
+    const uint64_t bp = (uint64_t)(uintptr_t)seq + (uint64_t)base;
+    // the lane's offset is made a 32-bit value of the very block that loads,
+    // where the instruction selection sees base + zero-extended offset
+    uint32_t lane_off = 16 * tid;
+    asm volatile("" : "+v"(lane_off));
+    if (interior) v0 = load16(global_bytes(own_sgprs(bp)) + lane_off);
+    else v0 = load_vec(seq, base, tid, sc.end);
+    if (lane_off < 16 * (kLoadVecs - kBlock)) {
+      if (interior) {
+        asm volatile("" : "+v"(lane_off));
+        v1 = load16(global_bytes(own_sgprs(bp + 16 * kBlock)) + lane_off);
+      } else {
+        v1 = load_vec(seq, base, kBlock + tid, sc.end);
+      }
+    }
+  };
+  prefetch(t_begin);
 
   uint32_t win_count = 0;
-  uint32_t count_seg = cur_seg;
+  uint32_t count_seg = pg.seg;
+
+  // pre-filter kernel: the LDS address of the lane's own slot in its wave's
+  // candidate list, computed once (the empty asm keeps the compiler from
+  // rebuilding it at each of the ~2.5 finishes per tile)
+  uint32_t cb_lane = 0;
+  if constexpr (PRE) {
+    cb_lane = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(s_cand + (tid >> 6) * kCandCap + (tid & 63));
+    asm volatile("" : "+v"(cb_lane));
+  }
 
   for (uint64_t tile = t_begin; tile < t_end;) {
-    Geom g = tile_geom(p, tile, cur_seg);
+    const TileGeom g = pg;  // this tile's: the prefetch below moves pg on
+    // The thread index as a value of this iteration: a lane predicate made from
+    // it (tid == 0, tid < kHaloWords) is one v_cmp here, where the
+    // compiler would hoist it out of the loop as a lane mask in an SGPR pair
+    // that it then spills (two v_readlane per use, and SGPRs are what is short).
+    int ltid = tid;
+    asm volatile("" : "+v"(ltid));
     if (g.seg != count_seg) {  // segment change: publish the previous segment
       add_windows(q.wins, win_count);
       win_count = 0;
       flush<MODE>(p, q, count_seg);
       count_seg = g.seg;
     }
-    const uint32_t shift = align_shift(p.seq, g.win0);
-    const uint64_t thresh = (MODE == kModeBottom) ? p.seg_thresh[g.seg] : 0;
+    const uint32_t shift = g.shift;
+    const uint64_t thresh = g.thresh;
     const bool last_of_chunk = tile + 1 == t_end;
-    if (dyn && tid == 0) {
+    if (dyn && ltid == 0) {
       if (tile == t_begin)
         grab = (unsigned long long)gridDim.x * p.chunk + atomicAdd(p.tile_queue, (unsigned long long)p.chunk);
       if (last_of_chunk) s_next = grab;
@@ -450,7 +599,7 @@ __global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(
       const uint32_t x0[5] = {v0.x, v0.y, v0.z, v0.w, 0u};
       pack16<true>(x0, 0, le, inv);
       store_word(tid, le, inv);
-      if (tid < kHaloWords) {
+      if (ltid < kHaloWords) {
         const uint32_t x1[5] = {v1.x, v1.y, v1.z, v1.w, 0u};
         pack16<true>(x1, 0, le, inv);
         store_word(kBlock + tid, le, inv);
@@ -475,20 +624,15 @@ __global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(
     // after the barrier; s_next is rewritten only at the next chunk's last
     // tile).  Every lane reads the same value: readfirstlane keeps the tile
     // counters and their 64-bit compares on the scalar unit.
-    uint64_t next_tile = !last_of_chunk ? tile + 1 : p.n_tiles;
+    uint64_t next_tile = tile + 1;
+    bool more = !last_of_chunk;  // a static range ends with its last tile
     if (last_of_chunk && dyn) {
-      const unsigned long long sn = s_next;
-      next_tile = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(sn >> 32)) << 32) |
-                  __builtin_amdgcn_readfirstlane((uint32_t)sn);
+      next_tile = uniform64(s_next);
+      more = uniform_less(next_tile, p.n_tiles);
     }
 
     // 3) prefetch the next tile while this one is hashed
-    if (next_tile < (dyn ? p.n_tiles : t_end)) {
-      Geom ng = tile_geom(p, next_tile, pf_seg);
-      pf_base = (int64_t)ng.win0 - align_shift(p.seq, ng.win0);
-      v0 = load_vec(p.seq, pf_base, tid, (int64_t)ng.seg_end);
-      if (tid < kLoadVecs - kBlock) v1 = load_vec(p.seq, pf_base, kBlock + tid, (int64_t)ng.seg_end);
-    }
+    if (more) prefetch(next_tile);
 
     // 4) 16 windows per lane: starts 16 (wbase + m) + r
     // A wave's windows read the invalid map of its 64 words and of the 2 after
@@ -606,6 +750,9 @@ __global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       };
+      // candidate lane + i of the list, from the lane's own slot address (held in a
+      // register; 16 i goes into the LDS instruction's offset field)
+      auto cand_at = [&](uint32_t i) { return (lds_u64x2*)(uintptr_t)(cb_lane + 16 * i); };
       const uint32_t pmask = p.low_mask & 0xFu;
       const uint32_t kbits = (uint32_t)p.kconst & pmask;
       // low bits of c = 2^s * d the pre-filter has not tested (none when s <= 4):
@@ -616,14 +763,19 @@ __global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(
       auto finish = [&](uint32_t n) {  // candidates [0, n), n <= 64
         __builtin_amdgcn_wave_barrier();
         if ((uint32_t)lane < n) {
-          const ulonglong2 e = cb[lane];
-          uint64_t y = mul_const<kMixMul>(e.x);
-          y ^= y >> 28;
-          const uint64_t f = y ^ p.kconst;
-          bool keep = mul_uniform(f, p.dinv) <= p.dlim;
-          if (rest_lo | rest_hi)  // wave-uniform
-            keep = keep && ((((uint32_t)f & rest_lo) | ((uint32_t)(f >> 32) & rest_hi)) == 0);
-          if (keep) emit<MODE>(p, q, g.seg, e.y, 0);
+          const u64x2 e = *cand_at(0);
+          // f = y ^ (y >> 28) ^ kconst, one three-input xor (v_bitop3_b32) per half
+          const uint64_t y = mul_const<kMixMul>(e.x);
+          const uint32_t ylo = (uint32_t)y, yhi = (uint32_t)(y >> 32);
+          const uint32_t flo = __builtin_amdgcn_bitop3_b32(ylo, funnel(yhi, ylo, 28), (uint32_t)p.kconst, 0x96);
+          const uint32_t fhi = __builtin_amdgcn_bitop3_b32(yhi, yhi >> 28, (uint32_t)(p.kconst >> 32), 0x96);
+          const uint64_t f = ((uint64_t)fhi << 32) | flo;
+          if (mul_uniform(f, p.dinv) <= p.dlim) {  // few lanes, often none: the rest is skipped then
+            bool keep = true;
+            if (rest_lo | rest_hi)  // wave-uniform
+              keep = ((flo & rest_lo) | (fhi & rest_hi)) == 0;
+            if (keep) emit<MODE>(p, q, g.seg, e.y, 0);
+          }
         }
         __builtin_amdgcn_wave_barrier();
       };
@@ -645,11 +797,11 @@ __global__ __launch_bounds__(kBlock, (min_waves<MODE, PRE>())) void scan_kernel(
           cnt += (uint32_t)__popcll(bal);
           if (cnt >= 64) {
             finish(64);
-            const uint32_t rest = cnt - 64;  // < 64: move them to the front
-            ulonglong2 t = make_ulonglong2(0, 0);
-            if ((uint32_t)lane < rest) t = cb[64 + lane];
-            __builtin_amdgcn_wave_barrier();
-            if ((uint32_t)lane < rest) cb[lane] = t;
+            // < 64: move them to the front.  Slots [64, 64 + rest) and [0, rest) do
+            // not overlap and a wave's LDS accesses run in program order, so each
+            // lane moves its own candidate, after the finish's reads of the front
+            const uint32_t rest = cnt - 64;
+            if ((uint32_t)lane < rest) *cand_at(0) = *cand_at(64);
             cnt = rest;
             set_cursor(rest);
           }
