@@ -29,7 +29,7 @@ extern "C" {
                               only): sks_sketch_set_downsample, sks_sketch_set_merge, sks_cluster,
                               sks_cluster_set, sks_gather, sks_gather_sets,
                               sks_ctx_set_gather_rounds, sks_search_topk,
-                              sks_search_topk_sets.  2: deduplicated join layout (masks, region
+                              sks_search_topk_sets, sks_sketch_set_filter.  2: deduplicated join layout (masks, region
                               ends), elem_words on the layout entry points,
                               sks_ctx_set_join_check; later additions within 2 (new symbols
                               only): sks_ani_rows, sks_intersect_layout_ani, sks_host_alloc,
@@ -254,6 +254,43 @@ int sks_sketch_set_downsample(sks_ctx* ctx, const sks_sketch_set* set, uint64_t 
 int sks_sketch_set_merge(sks_ctx* ctx, const sks_sketch_set* const* sets, uint32_t n_sets,
                          const uint32_t* group_off, const uint32_t* members, uint32_t n_groups,
                          sks_sketch_set** out);
+/* Subtract or intersect: a new set on the context's device with `set`'s number
+ * of sketches, sketch i holding the elements of `set`'s sketch i that are absent
+ * from (SKS_FILTER_SUBTRACT) or present in (SKS_FILTER_INTERSECT) sketch
+ * filter_of[i] of `filters`.  The elements keep the source order, so they stay
+ * ascending and unique; wide elements are compared as whole 128-bit values.  As
+ * the elements are masked canonical k-mers kept on their own hash, at one
+ * FracMinHash scale the result is the sketch of the difference (intersection)
+ * of the two k-mer sets, and every other call takes it.
+ *  filter_of: a host array of set->n entries.  UINT32_MAX: sketch i is copied
+ *    unchanged, whatever the kind.  Several sketches may name the same filter.
+ *    NULL: every sketch uses filter 0, allowed only when `filters` holds exactly
+ *    one sketch (else SKS_E_ARG).  filters == set is allowed.
+ *  Carried over from `set`: window, mask, elem_words, the whole policy, per-sketch
+ *    windows and names (sks_sketch_set_info of the result equals the source's).
+ *    Neither input is modified.
+ *  Both sets must be SKS_FRAC_MOD (a bottom-s set on either side is SKS_E_ARG
+ *    naming "policy kind": the bottom-s sketch of a difference is not a part of
+ *    the bottom-s sketches) and agree in window, mask, elem_words, hash flavour,
+ *    nonce and policy param (else SKS_E_ARG naming "window", "mask",
+ *    "elem_words", "flavour", "nonce" or "policy param"); nothing is
+ *    downsampled implicitly.
+ *  An empty source sketch gives an empty sketch; an empty filter sketch makes
+ *    SUBTRACT copy and INTERSECT empty; a set of no sketches gives a set of none.
+ * SKS_E_ARG, decided on the host before anything is launched: a null ctx, set,
+ * filters or out (before any device is touched), an unknown kind, a filter_of[i]
+ * that is neither UINT32_MAX nor below the filters' number of sketches (the
+ * message names i and the index), a set on another device than the context's.
+ * *out is NULL on every failure.
+ * Waits for the context's stream once, to read the new sizes back; the elements
+ * are then written by a kernel queued on that stream (sks_ctx_synchronize waits
+ * for it; both inputs may be freed with sks_sketch_set_free at once). */
+typedef enum sks_filter_kind {
+  SKS_FILTER_SUBTRACT = 0,  /* keep x iff x is not in the filter sketch */
+  SKS_FILTER_INTERSECT = 1  /* keep x iff x is in the filter sketch     */
+} sks_filter_kind;
+int sks_sketch_set_filter(sks_ctx* ctx, const sks_sketch_set* set, const sks_sketch_set* filters,
+                          const uint32_t* filter_of, int kind, sks_sketch_set** out);
 
 /* ---- ordered k-mer lists: nucleotide_string_list_to_kmers (kmer_sliding.cpp:112-238) ---
  * Every selected window of every segment, in stream order, duplicates kept —

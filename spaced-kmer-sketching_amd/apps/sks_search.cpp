@@ -19,6 +19,13 @@
 //       the sketches are found by name across the input databases, the groups
 //       come in order of first appearance and name the output's sketches; the
 //       result equals a database indexed from each group's sequences together
+//   sks-search subtract <db.sks> <filter.sks> <out.sks>
+//   sks-search intersect <db.sks> <filter.sks> <out.sks>
+//       every sketch of the database without (subtract) or within (intersect)
+//       the union of all sketches of filter.sks (sks_sketch_set_merge, one group
+//       of all, then sks_sketch_set_filter): host or contaminant k-mers out of
+//       every sample, or the part of every sample inside a pangenome.  Both
+//       databases must share window, mask, scale and hash; names kept
 //   sks-search cluster <db.sks> <min_containment> <out.tsv> [<reps.sks>]
 //       single-linkage clusters of the database (sks_cluster_set, min_shared 1):
 //       two sketches are linked when the larger of their two containments is at
@@ -101,10 +108,12 @@ int usage(const char* argv0) {
                "       %s query <db.sks> <min_containment> <out.csv> <fasta files...>\n"
                "       %s downsample <in.sks> <c> <out.sks>\n"
                "       %s merge <out.sks> <groups.tsv> <in.sks> [<in.sks> ...]\n"
+               "       %s subtract <db.sks> <filter.sks> <out.sks>\n"
+               "       %s intersect <db.sks> <filter.sks> <out.sks>\n"
                "       %s cluster <db.sks> <min_containment> <out.tsv> [<reps.sks>]\n"
                "       %s gather <db.sks> <min_shared> <out.csv> <fasta files...>\n"
                "       %s top <db.sks> <k> <out.csv> <fasta files...>\n",
-               argv0, argv0, argv0, argv0, argv0, argv0, argv0);
+               argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0);
   return 64;
 }
 
@@ -236,6 +245,34 @@ int run(int argc, char* argv[]) {
     std::printf("%u sketches -> %s\n", sks_sketch_set_num(merged), argv[2]);
     sks_sketch_set_free(merged);
     for (sks_sketch_set* db : dbs) sks_sketch_set_free(db);
+    sks_ctx_destroy(ctx);
+    return 0;
+  }
+  if ((mode == "subtract" || mode == "intersect") && argc == 5) {
+    check(sks_ctx_create(0, nullptr, &ctx));
+    sks_sketch_set *db = nullptr, *filter = nullptr, *united = nullptr, *kept = nullptr;
+    check(sks_sketch_set_load(ctx, argv[2], &db));
+    check(sks_sketch_set_load(ctx, argv[3], &filter));
+    // the filter database as one sketch: one group of all its sketches
+    const uint32_t n_filter = sks_sketch_set_num(filter);
+    std::vector<uint32_t> members(n_filter);
+    for (uint32_t i = 0; i < n_filter; ++i) members[i] = i;
+    const uint32_t group_off[2] = {0, n_filter};
+    check(sks_sketch_set_merge(ctx, &filter, 1, group_off, members.data(), 1, &united));
+    check(sks_sketch_set_filter(ctx, db, united, nullptr,
+                                mode == "subtract" ? SKS_FILTER_SUBTRACT : SKS_FILTER_INTERSECT, &kept));
+    check(sks_ctx_synchronize(ctx));
+    check(sks_sketch_set_save(kept, argv[4]));
+    const uint32_t n = sks_sketch_set_num(kept);
+    std::vector<uint32_t> sizes(n);
+    if (n) check(sks_sketch_set_sizes(kept, sizes.data()));
+    unsigned long long elements = 0;
+    for (uint32_t v : sizes) elements += v;
+    std::printf("%u sketches, %llu elements -> %s\n", n, elements, argv[4]);
+    sks_sketch_set_free(kept);
+    sks_sketch_set_free(united);
+    sks_sketch_set_free(filter);
+    sks_sketch_set_free(db);
     sks_ctx_destroy(ctx);
     return 0;
   }

@@ -2,7 +2,8 @@
 // copy of a device sketch set (FracMinHash 1/c -> 1/c', bottom-s -> bottom-s')
 // made from the set's own elements by the filter kernels of downsample.hip.
 // downsample_arrays, the work after the argument checks, also cuts the bottom-s
-// sketches of sks_sketch_set_merge (merge_api.cpp).
+// sketches of sks_sketch_set_merge (merge_api.cpp); the chunk prefixes and the
+// sizing tail also serve sks_sketch_set_filter (filter_api.cpp).
 #include <numeric>
 
 #include "sks_ctx.hpp"
@@ -14,6 +15,17 @@ int sks::reserve_chunk_counters(sks_ctx* c, uint64_t n_chunks) {
   SKS_HIP(c->flag.reserve((n_chunks + 1) * sizeof(uint32_t)));
   SKS_HIP(c->pos.reserve((n_chunks + 1) * sizeof(uint64_t)));
   return SKS_OK;
+}
+
+void sks::chunk_prefixes(const std::vector<uint32_t>& sizes, std::vector<uint64_t>* chunk_off,
+                         std::vector<uint64_t>* dense_off) {
+  const size_t n = sizes.size();
+  chunk_off->assign(n + 1, 0);
+  dense_off->assign(n + 1, 0);
+  for (size_t g = 0; g < n; ++g) {
+    (*chunk_off)[g + 1] = (*chunk_off)[g] + (sizes[g] + (uint64_t)kDownsampleChunk - 1) / kDownsampleChunk;
+    (*dense_off)[g + 1] = (*dense_off)[g] + sizes[g];
+  }
 }
 
 int sks::size_set_from_counts(sks_ctx* c, const char* who, const char* too_large, uint64_t n_chunks,
@@ -46,13 +58,12 @@ int sks::downsample_arrays(sks_ctx* c, const char* who, const uint64_t* d_data, 
   const int ew = like.elem_words;
 
   // chunks and elements before each sketch
-  std::vector<uint64_t> chunk_off(n + 1, 0), dense_off(n + 1, 0);
+  std::vector<uint64_t> chunk_off, dense_off;
+  chunk_prefixes(src_sizes, &chunk_off, &dense_off);
   uint64_t max_len = 0;
   bool selects = false;  // bottom-s: a sketch holds more than `param` elements
   for (uint32_t g = 0; g < n; ++g) {
     const uint64_t sz = src_sizes[g];
-    chunk_off[g + 1] = chunk_off[g] + (sz + kDownsampleChunk - 1) / kDownsampleChunk;
-    dense_off[g + 1] = dense_off[g] + sz;
     max_len = std::max(max_len, sz);
     selects = selects || sz > param;
   }

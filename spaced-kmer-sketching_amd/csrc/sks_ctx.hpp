@@ -1,7 +1,7 @@
 // What the C-ABI translation units that run on a device share (ctx.cpp,
 // host_mem.cpp, sketch_set.cpp, kmer_list.cpp, build.cpp, build_post.cpp,
 // pairs.cpp, search_api.cpp, topk_api.cpp, cluster_api.cpp, gather_api.cpp,
-// downsample_api.cpp, merge_api.cpp): the context, the sketch set and k-mer
+// downsample_api.cpp, merge_api.cpp, filter_api.cpp): the context, the sketch set and k-mer
 // list with the device blocks they own, the error macros, the metadata arena,
 // SketchSpan and the group bounds of the set-level calls (their device-free
 // rules: set_rules.hpp) and small argument helpers.
@@ -20,6 +20,7 @@
 #include "code_objects.hpp"
 #include "device_mem.hpp"
 #include "downsample.hpp"
+#include "filter.hpp"
 #include "gather.hpp"
 #include "ingress.hpp"
 #include "intersect.hpp"
@@ -282,6 +283,10 @@ inline int fail_invalid_layout(const std::string& me, const std::string& what, c
 int downsample_arrays(sks_ctx* c, const char* who, const uint64_t* d_data, const uint64_t* d_starts,
                       const uint32_t* d_sizes, const std::vector<uint32_t>& src_sizes, const sks_sketch_set& like,
                       uint64_t param, SetPtr* out);
+// chunk_off[g], dense_off[g]: the kDownsampleChunk-element chunks and the elements before
+// sketch g of sketches of these sizes ([n + 1] each)
+void chunk_prefixes(const std::vector<uint32_t>& sizes, std::vector<uint64_t>* chunk_off,
+                    std::vector<uint64_t>* dense_off);
 // The tail of a call whose count kernel decides the new sketches' sizes: kept
 // elements per kDownsampleChunk-element chunk in chunk_counts(c), reserved with
 // chunk_offs(c) before that kernel is queued.  size_set_from_counts queues

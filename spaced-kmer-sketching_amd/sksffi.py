@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("SKS_LIB") or os.path.join(PKG_DIR, "lib", "libsks.so"
 
 SKS_FRAC_MOD = 0
 SKS_BOTTOM_S = 1
+SKS_FILTER_SUBTRACT, SKS_FILTER_INTERSECT = 0, 1  # sks_filter_kind
+FILTER_NONE = 0xFFFFFFFF  # a filter_of entry: the sketch is copied unchanged
 INTERSECT_AUTO, INTERSECT_MERGE, INTERSECT_JOIN, INTERSECT_GLOBAL = 0, 1, 2, 3
 FRAC_POST_AUTO, FRAC_POST_GENERAL, FRAC_POST_FUSED = 0, 1, 2
 BUILD_PATH_GENERAL, BUILD_PATH_FUSED, BUILD_PATH_FUSED_THEN_GENERAL_POST = 0, 1, 2
@@ -77,7 +79,7 @@ EXPORTED = [
     "sks_search", "sks_search_sets", "sks_ctx_set_search_batch", "sks_sketch_set_downsample",
     "sks_sketch_set_merge", "sks_cluster", "sks_cluster_set",
     "sks_gather", "sks_gather_sets", "sks_ctx_set_gather_rounds",
-    "sks_search_topk", "sks_search_topk_sets",
+    "sks_search_topk", "sks_search_topk_sets", "sks_sketch_set_filter",
 ]
 
 # sks_hit (include/sks.h): one record of Context.search's result
@@ -205,6 +207,7 @@ def lib():
     L.sks_sketch_set_concat.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
     L.sks_sketch_set_downsample.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp)]
     L.sks_sketch_set_merge.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(vp)]
+    L.sks_sketch_set_filter.argtypes = [vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
     L.sks_kmer_list_build.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, u64p,
                                       C.POINTER(Policy), C.POINTER(vp)]
     L.sks_windows_dense.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, u64p, vp, vp]
@@ -682,6 +685,25 @@ class Context:
         check(lib().sks_sketch_set_merge(self.h, arr, len(sets), off.ctypes.data, mem.ctypes.data, len(groups),
                                          C.byref(h)))
         return SketchSet(h)
+
+    def filter(self, sketch_set, filters, kind, filter_of=None):
+        """sks_sketch_set_filter: sketch i of the result holds the elements of sketch i
+        of `sketch_set` absent from (SKS_FILTER_SUBTRACT) or present in
+        (SKS_FILTER_INTERSECT) sketch filter_of[i] of `filters`; FILTER_NONE copies
+        sketch i.  filter_of None: every sketch against the one sketch of `filters`."""
+        fo = None if filter_of is None else np.ascontiguousarray(list(filter_of) + [0], dtype=np.uint32)
+        if fo is not None and len(fo) - 1 != sketch_set.n:
+            raise ValueError(f"filter_of has {len(fo) - 1} entries for {sketch_set.n} sketches")
+        h = C.c_void_p()
+        check(lib().sks_sketch_set_filter(self.h, sketch_set.h, filters.h, None if fo is None else fo.ctypes.data,
+                                          int(kind), C.byref(h)))
+        return SketchSet(h)
+
+    def subtract(self, sketch_set, filters, filter_of=None):
+        return self.filter(sketch_set, filters, SKS_FILTER_SUBTRACT, filter_of)
+
+    def intersect(self, sketch_set, filters, filter_of=None):
+        return self.filter(sketch_set, filters, SKS_FILTER_INTERSECT, filter_of)
 
     def intersect_pairs(self, data_ptr, starts_ptr, sizes_ptr, elem_words, a_ptr, b_ptr,
                         n_pairs, out_ptr):
