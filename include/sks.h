@@ -398,6 +398,14 @@ uint32_t sks_join_layout_log_b(uint32_t max_sketch_size);
 /* Block-bucket population (entries) one join chunk holds; larger buckets are
  * joined in sub-chunks (exact, slower). */
 uint32_t sks_join_layout_capacity(void);
+/* log2 of the value groups per region that a layout build of n_blocks blocks
+ * (of 64 sketches) with 2^log_b buckets takes in this process (0..3; a region's
+ * buckets: min(2^log_b, 8 groups' worth)).  Read-only; for tests and diagnostics. */
+uint32_t sks_join_layout_region_log(uint32_t n_blocks, uint32_t log_b);
+/* How this process cuts a join call of `tiles` tiles over a layout of 2^log_b
+ * buckets: workgroups per tile and whole tiles per launch (either may be NULL).
+ * Read-only; for tests and diagnostics.  Returns SKS_E_ARG for log_b > 14. */
+int sks_join_launch_plan(uint64_t tiles, uint32_t log_b, uint32_t* n_groups, uint64_t* tiles_per_launch);
 /* Value groups of a layout with 2^log_b buckets (bounds hold groups + 1 values). */
 uint32_t sks_join_layout_groups(uint32_t log_b);
 /* Words of one block's boff row: 2^log_b bucket starts + room for the region

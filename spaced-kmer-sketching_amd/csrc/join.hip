@@ -30,6 +30,7 @@
 #include "code_objects.hpp"
 #include "join.hpp"
 #include "join_common.hpp"
+#include "join_plan.hpp"
 #include "sks_ani.hpp"
 #include "wave_prims.hpp"
 
@@ -47,9 +48,6 @@ using jc::kv_load;
 using jc::sym_tile;
 
 constexpr int kTile = 64;
-// workgroups per launch at most (HIP caps a grid at 2^32 - 1 work-items);
-// larger grids are cut into slices
-constexpr uint64_t kMaxGrid = 1ull << 22;
 // 512 threads (8 waves): four workgroups per CU for u64 values (32 waves),
 // three for 128-bit values, hide the LDS round trips of the insert and probe chains
 constexpr int kJB = 512;
@@ -68,6 +66,11 @@ constexpr int kJRowPf = 1;   // row entries per thread held in registers per chu
 // piecewise, at most kJPieces regions per chunk)
 constexpr int kJWinLog = 6, kJWin = 1 << kJWinLog;
 static_assert(kJWinLog <= 6, "a window's buckets are scanned by one wave");
+// join_plan.hpp (no HIP) restates the window and the layout's geometry limits;
+// a launch of kJoinMaxGrid workgroups stays below HIP's 2^32 - 1 work-items
+static_assert(kJoinWinLog == (uint32_t)kJWinLog && kJoinGroupLog == jc::kGLog && kJoinMaxLogB == jc::kMaxLogB,
+              "join_plan.hpp geometry");
+static_assert(kJoinMaxGrid * kJB < (1ull << 32), "grid size");
 constexpr uint32_t kJPieces = 4;
 // 12 planes hold counts below 2^12 per workgroup; a carry out of the top plane
 // (a pair sharing >= 4096 values in one workgroup's buckets) is added to the
@@ -675,18 +678,19 @@ __global__ __launch_bounds__(kJB, EW == 1 ? 8 : 2) void k_join(JoinArgs a) {
 template <int EW, bool CHECK, bool PIECES>
 hipError_t launch_join_slices(JoinArgs ja, uint64_t tile_begin, uint64_t tile_end, bool packed, int32_t* out,
                               uint32_t* tile_done, hipStream_t s) {
-  const uint64_t tiles_per_launch = std::max<uint64_t>(1, kMaxGrid / ja.n_groups);
+  const uint64_t tiles_per_launch = join_plan_tiles_per_launch(ja.n_groups);
   // diagonal tiles last: a symmetric launch of every tile (no tile list, one slice)
-  const uint64_t all_sym = (uint64_t)ja.n_col_blocks * (ja.n_col_blocks + 1) / 2;
-  ja.diag_last = ja.sym && !ja.tiles && tile_begin == 0 && tile_end == all_sym &&
-                         tile_end <= tiles_per_launch && getenv("SKS_JOIN_TILE_ORDER") == nullptr
+  ja.diag_last = join_plan_diag_last(ja.sym != 0, ja.tiles != nullptr, tile_begin, tile_end, ja.n_col_blocks,
+                                     tiles_per_launch, getenv("SKS_JOIN_TILE_ORDER") != nullptr)
                      ? 1
                      : 0;
-  for (uint64_t t0 = tile_begin; t0 < tile_end; t0 += tiles_per_launch) {
-    const uint64_t nt = std::min(tiles_per_launch, tile_end - t0);
-    ja.tile_begin = t0;
-    if (packed) ja.out = out + (t0 - tile_begin) * (uint64_t)(kTile * kTile);
-    if (ja.ani) ja.tile_done = tile_done + (t0 - tile_begin);
+  const uint64_t slices = join_plan_slices(tile_begin, tile_end, tiles_per_launch);
+  for (uint64_t sl = 0; sl < slices; ++sl) {
+    const uint64_t nt = join_plan_slice_tiles(tile_begin, tile_end, sl, tiles_per_launch);
+    const uint64_t first = join_plan_slice_offset(tile_begin, sl, tiles_per_launch);  // tiles before this launch
+    ja.tile_begin = join_plan_slice_begin(tile_begin, sl, tiles_per_launch);
+    if (packed) ja.out = out + first * (uint64_t)(kTile * kTile);
+    if (ja.ani) ja.tile_done = tile_done + first;
     hipLaunchKernelGGL((k_join<EW, CHECK, PIECES>), dim3((unsigned)(nt * ja.n_groups)), dim3(kJB), 0, s, ja);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -705,10 +709,18 @@ uint32_t join_cap() {  // SKS_JOIN_CAP (diagnostics) is clamped to [64, kJCap]
 
 // Bucket count for the join: mean raw block-bucket population ~ cap / 6, so a
 // chunk holds several whole buckets (fewer after deduplication).
-uint32_t join_log_b(uint32_t max_size) {
-  uint32_t log_b = 0;
-  while ((1ull << log_b) * (join_cap() / 6) < 64ull * max_size && log_b < jc::kMaxLogB) ++log_b;
-  return log_b;
+uint32_t join_log_b(uint32_t max_size) { return join_plan_log_b(max_size, join_cap()); }
+
+// SKS_JOIN_WGS (diagnostics): the total number of workgroups of a join call, 0: the default rule
+static uint64_t join_wgs() {
+  static const uint64_t wgs_env = getenv("SKS_JOIN_WGS") ? strtoull(getenv("SKS_JOIN_WGS"), 0, 10) : 0;
+  return wgs_env;
+}
+
+void join_launch_plan(uint64_t tiles, uint32_t log_b, uint32_t* n_groups, uint64_t* tiles_per_launch) {
+  const JoinGroups jg = join_plan_groups(1u << std::min<uint32_t>(log_b, jc::kMaxLogB), tiles, join_wgs());
+  if (n_groups) *n_groups = jg.n_groups;
+  if (tiles_per_launch) *tiles_per_launch = join_plan_tiles_per_launch(jg.n_groups);
 }
 
 unsigned long long join_check_take() {
@@ -761,31 +773,16 @@ hipError_t join_launch(const JoinLayout& rows, uint32_t r_blk0, const JoinLayout
     ja.root_size = ani->root_size;
   }
   uint32_t* tile_done = ani ? ani->tile_done : nullptr;
-  // bucket groups per tile: ~128 buckets per workgroup (a workgroup's start-up —
-  // clearing its table and count planes — and its count flush, up to 4096 global
-  // atomics on a tile of related genomes, are then small beside its chunks), at
-  // least ~1024 workgroups in all, at least 16 buckets each (round 3 sweep,
-  // config 4: 4352 workgroups 0.681 ms against 2176: 0.705, 8704: 0.742).
-  // SKS_JOIN_WGS (diagnostics) sets the total instead.  The ~128-buckets floor
-  // only applies while the grid is small (<= 64K workgroups); with very many
-  // tiles a tile gets fewer, larger groups (down to one).
-  static const uint64_t wgs_env = getenv("SKS_JOIN_WGS") ? strtoull(getenv("SKS_JOIN_WGS"), 0, 10) : 0;
-  uint64_t want = wgs_env ? (wgs_env + tiles - 1) / tiles
-                          : std::max<uint64_t>(std::min<uint64_t>((B + 127) / 128, (65536 + tiles - 1) / tiles),
-                                               (1024 + tiles - 1) / tiles);
-  if (!wgs_env) want = std::min<uint64_t>(want, std::max<uint32_t>(1, B / 16));
-  const uint32_t groups = (uint32_t)std::min<uint64_t>(B, std::max<uint64_t>(1, want));
-  ja.buckets_per_group = (B + groups - 1) / groups;
-  ja.n_groups = (B + ja.buckets_per_group - 1) / ja.buckets_per_group;
-  // windows across regions (PIECES) unless both layouts have 64-bucket regions:
-  // known only for one layout covering all n sketches (the build picks its
-  // region size from its block count, join_layout_region_log); a tile list
-  // joins per-rank layouts, small ones
+  // bucket groups per tile (join_plan.hpp join_plan_groups; SKS_JOIN_WGS sets
+  // the call's total number of workgroups instead)
+  const JoinGroups jg = join_plan_groups(B, tiles, join_wgs());
+  ja.buckets_per_group = jg.buckets_per_group;
+  ja.n_groups = jg.n_groups;
+  // windows across regions (PIECES) unless both layouts have 64-bucket regions
+  // (join_plan_contiguous)
   const bool one_layout = rows.vals == cols.vals && rows.boff == cols.boff;
-  const bool big = (!d_tiles && r_blk0 == 0 && c_blk0 == 0 && one_layout &&
-                    jc::lay_rb_log(log_b, join_layout_region_log(n_cb, log_b)) >= (uint32_t)kJWinLog) ||
-                   (layout_rg >= 0 && one_layout && jc::lay_rb_log(log_b, (uint32_t)layout_rg) >= (uint32_t)kJWinLog);
-  const bool pieces = !big;
+  const bool pieces = !join_plan_contiguous(log_b, join_layout_region_log(n_cb, log_b), layout_rg, one_layout,
+                                            d_tiles != nullptr, r_blk0, c_blk0);
 #define SKS_JOIN_LAUNCH(E, C, P) launch_join_slices<E, C, P>(ja, tile_begin, tile_end, packed, out, tile_done, s)
   if (ew == 1) {
     if (pieces) return check ? SKS_JOIN_LAUNCH(1, true, true) : SKS_JOIN_LAUNCH(1, false, true);

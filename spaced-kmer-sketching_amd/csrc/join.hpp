@@ -19,6 +19,10 @@ struct JoinLayout {
 };
 uint32_t join_cap();                       // entries per join chunk (table capacity)
 uint32_t join_log_b(uint32_t max_size);    // bucket count for a largest sketch of max_size
+// how this process cuts a join call of `tiles` tiles over a layout of 2^log_b
+// buckets (join_plan.hpp, with SKS_JOIN_WGS applied): workgroups per tile and
+// whole tiles per launch
+void join_launch_plan(uint64_t tiles, uint32_t log_b, uint32_t* n_groups, uint64_t* tiles_per_launch);
 // G = 2^log_b / 8 value groups (>= 1); bounds: (G + 1) values of ew words.
 // join_layout_bounds computes the group bounds of a set (the median over up
 // to 64 sample sketches of their quantiles).  join_layout_build: the layout of sketches (data,

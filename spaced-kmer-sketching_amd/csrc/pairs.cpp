@@ -101,6 +101,14 @@ int sks_intersect_sym(sks_ctx* c, const uint64_t* d_data, const uint64_t* d_star
 
 uint32_t sks_join_layout_log_b(uint32_t max_sketch_size) { return sks::join_log_b(max_sketch_size); }
 uint32_t sks_join_layout_capacity(void) { return sks::join_cap(); }
+uint32_t sks_join_layout_region_log(uint32_t n_blocks, uint32_t log_b) {
+  return log_b > 14 ? 0u : sks::join_layout_region_log(n_blocks, log_b);
+}
+int sks_join_launch_plan(uint64_t tiles, uint32_t log_b, uint32_t* n_groups, uint64_t* tiles_per_launch) {
+  if (log_b > 14) return sks::fail(SKS_E_ARG, "sks_join_launch_plan: log_b too large");
+  sks::join_launch_plan(tiles, log_b, n_groups, tiles_per_launch);
+  return SKS_OK;
+}
 uint32_t sks_join_layout_groups(uint32_t log_b) { return sks::join_layout_groups(log_b); }
 uint32_t sks_join_layout_boff_words(uint32_t log_b) { return log_b > 14 ? 0u : sks::join_layout_boff_words(log_b); }
 

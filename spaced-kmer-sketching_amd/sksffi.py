@@ -80,6 +80,7 @@ EXPORTED = [
     "sks_sketch_set_merge", "sks_cluster", "sks_cluster_set",
     "sks_gather", "sks_gather_sets", "sks_ctx_set_gather_rounds",
     "sks_search_topk", "sks_search_topk_sets", "sks_sketch_set_filter",
+    "sks_join_layout_region_log", "sks_join_launch_plan",
 ]
 
 # sks_hit (include/sks.h): one record of Context.search's result
@@ -163,6 +164,10 @@ def lib():
     L.sks_join_layout_log_b.restype = C.c_uint32
     L.sks_join_layout_capacity.argtypes = []
     L.sks_join_layout_capacity.restype = C.c_uint32
+    L.sks_join_layout_region_log.argtypes = [C.c_uint32, C.c_uint32]
+    L.sks_join_layout_region_log.restype = C.c_uint32
+    L.sks_join_launch_plan.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.sks_join_launch_plan.restype = C.c_int
     L.sks_join_layout_build.argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, vp,
                                         vp, vp, vp, vp, C.POINTER(C.c_uint32)]
     L.sks_join_layout_bounds.argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint32, C.c_uint32, vp]
@@ -301,6 +306,20 @@ def join_layout_log_b(max_sketch_size):
 
 def join_layout_capacity():
     return int(lib().sks_join_layout_capacity())
+
+
+def join_layout_region_log(n_blocks, log_b):
+    """sks_join_layout_region_log: log2 of the value groups per region a layout
+    build of n_blocks blocks takes in this process (SKS_LAYOUT_RG applied)."""
+    return int(lib().sks_join_layout_region_log(n_blocks, log_b))
+
+
+def join_launch_plan(tiles, log_b):
+    """sks_join_launch_plan: (workgroups per tile, tiles per launch) of a join
+    call of `tiles` tiles in this process (SKS_JOIN_WGS applied)."""
+    g, t = C.c_uint32(0), C.c_uint64(0)
+    check(lib().sks_join_launch_plan(int(tiles), log_b, C.byref(g), C.byref(t)))
+    return int(g.value), int(t.value)
 
 
 def join_layout_groups(log_b):

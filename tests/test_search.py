@@ -339,3 +339,108 @@ def test_bottom_s_of_different_s(gpu):
     assert case.Q.info()["param"] == 128 and case.R.info()["param"] == 256
     thr = _threshold(case.shared, case.qsizes)
     _check(ctx.search(case.Q, case.R, min_containment=thr), case.expected(min_containment=thr))
+
+
+# ---- few queries against many large references ---------------------------------------------------
+# The shape sks-search exists for.  The query layout and each reference batch's
+# layout take their region size from their own block count
+# (join_layout_region_log), so one block of queries against batches of 2 or of 4
+# and more blocks joins layouts of different region sizes in one k_join launch:
+# a window of 64 buckets is four regions of the rows and two or one of the
+# columns.  Sketches of more than 21 760 elements put the layouts at 2^14
+# buckets, where those region logs are 1, 2 and 3.
+
+LARGE_RATES = [0.0, 0.002, 0.01, 0.03]
+_LARGE_HOST = {}  # (nr, w, k) -> (qsizes, rsizes, shared): the host side, computed once per process
+
+
+def _shared_indexed(Q, R):
+    """shared[q, r] with the references indexed once: the lo words of all their
+    elements with the owning reference, one sort.  A query element's candidates
+    are the run of equal lo words; it is shared with those whose hi word is
+    equal too (hi is 0 for 64-bit elements)."""
+    parts = [R.sketch(j) for j in range(R.n)]
+    owner = np.repeat(np.arange(R.n), [len(p) for p in parts])
+    allr = np.concatenate(parts)
+    order = np.argsort(allr[:, 0], kind="stable")
+    slo, shi, sown = allr[order, 0], allr[order, 1], owner[order]
+    shared = np.zeros((Q.n, R.n), dtype=np.int32)
+    for i in range(Q.n):
+        a = Q.sketch(i)
+        if not len(a):
+            continue
+        b = np.searchsorted(slo, a[:, 0], "left")
+        cnt = np.searchsorted(slo, a[:, 0], "right") - b
+        idx = np.repeat(b - (np.cumsum(cnt) - cnt), cnt) + np.arange(int(cnt.sum()))
+        ok = shi[idx] == np.repeat(a[:, 1], cnt)
+        shared[i] = np.bincount(sown[idx[ok]], minlength=R.n)
+    return shared
+
+
+class LargeCase:
+    """6 queries (one empty, one a reference's genome, one related to nothing)
+    against nr references of 23-26 kb in families of 6 ancestors at rates
+    0 .. 0.03, FracMinHash c = 1: every sketch holds about 23 000 elements."""
+
+    def __init__(self, torch, ctx, nr, w, k):
+        self.w, self.k = w, k
+        self.mask = sksffi.mask_generate(w, k, 0)
+        length = lambda i: 23000 + (i * 997) % 3001  # noqa: E731
+        qs = [(length(0), 200, 0, 0.0), (length(1), 201, 7001, 0.01), (EMPTY, 202, 0, 0.0),
+              (length(3), 202, 7003, 0.03), (length(4), 203, 0, 0.0), (length(5), 299, 0, 0.0)]
+        rs = [(length(i + 7), 200 + i % 6, 8000 + i, LARGE_RATES[(i // 6) % len(LARGE_RATES)]) for i in range(nr)]
+        rs[24] = qs[0]                            # a reference that is a query's genome
+        rs[nr - 30] = (EMPTY,) + rs[nr - 30][1:]  # and an empty reference
+        self.Q = _build(torch, ctx, qs, w, self.mask, sksffi.SKS_FRAC_MOD, 1)
+        self.R = _build(torch, ctx, rs, w, self.mask, sksffi.SKS_FRAC_MOD, 1)
+        qsizes, rsizes = self.Q.sizes().astype(np.int64), self.R.sizes().astype(np.int64)
+        key = (nr, w, k)
+        if key not in _LARGE_HOST:
+            shared = _shared_indexed(self.Q, self.R)
+            # the index against the pairwise reference of this file, on a corner
+            assert np.array_equal(shared[:2, 23:26], _shared(_keys(self.Q)[:2], _keys(self.R)[23:26]))
+            _LARGE_HOST[key] = (qsizes, rsizes, shared)
+        self.qsizes, self.rsizes, self.shared = _LARGE_HOST[key]
+        assert np.array_equal(qsizes, self.qsizes) and np.array_equal(rsizes, self.rsizes)  # the same sets again
+        # the premise: 2^14 buckets, and a region log per block count
+        assert qsizes[2] == 0 and rsizes[nr - 30] == 0 and rsizes[rsizes > 0].min() > 21760
+        assert sksffi.join_layout_log_b(int(max(qsizes.max(), rsizes.max()))) == 14
+        assert [sksffi.join_layout_region_log(b, 14) for b in (1, 2, 4, 6)] == [1, 2, 3, 3]
+        # from nothing to everything
+        # (unrelated genomes of this size can share a chance k-mer or two)
+        assert self.shared[0, 24] == qsizes[0] and self.shared[5].sum() <= 3 and not self.shared[2].any()
+        assert self.shared[:, 4::6].sum() <= 3 and len(np.unique(self.shared[self.shared > 0])) > 10
+
+    def expected(self, **kw):
+        return _expected(self.shared, self.qsizes, self.k, **kw)
+
+
+@pytest.fixture(scope="module")
+def large(gpu):
+    torch, ctx = gpu
+    return LargeCase(torch, ctx, 330, 31, 21)
+
+
+def test_few_queries_many_large_references(gpu, large):
+    """6 x 330 at 2^14 buckets: one query block (region log 1) against the six
+    reference blocks in one batch (3), one block a batch (1), two (2), and four
+    then two (3 and 2 in one call).  Every run is the host's list."""
+    _, ctx = gpu
+    assert large.Q.n == 6 and (large.R.n + 63) // 64 == 6 and large.R.n % 64
+    want = large.expected()
+    assert len(want) > 200
+    try:
+        for blocks in (0, 1, 2, 4):
+            ctx.set_search_batch(blocks)
+            _check(ctx.search(large.Q, large.R), want)
+    finally:
+        ctx.set_search_batch(0)
+
+
+def test_few_queries_many_large_references_wide(gpu):
+    """The same at w = 45 / k = 30 (128-bit elements): four reference blocks in
+    one batch, region log 3 against the queries' 1."""
+    torch, ctx = gpu
+    case = LargeCase(torch, ctx, 230, 45, 30)
+    assert case.Q.elem_words == 2 and (case.R.n + 63) // 64 == 4
+    _check(ctx.search(case.Q, case.R), case.expected())

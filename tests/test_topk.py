@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 import sksffi
-from test_search import EMPTY, _build, _keys, _shared, _spec, _threshold
+from test_search import EMPTY, LargeCase, _build, _keys, _shared, _spec, _threshold
 
 pytestmark = pytest.mark.gpu
 
@@ -213,6 +213,26 @@ def test_agrees_with_search(gpu, frac):
     for f, g in (("query", "query"), ("ref", "ref"), ("shared", "shared"), ("query_size", "query_size"),
                  ("containment", "score"), ("ani", "ani")):
         assert np.ascontiguousarray(want[f]).tobytes() == np.ascontiguousarray(got[g]).tobytes(), f
+
+
+def test_few_queries_many_large_references(gpu):
+    """The large case of tests/test_search.py (6 queries x 330 references of
+    about 23 000 elements: one query block of region log 1 against reference
+    batches of region log 3 and 2): the 5 best per query by containment in the
+    query, in one batch and in batches of four and two blocks."""
+    torch, ctx = gpu
+    case = LargeCase(torch, ctx, 330, 31, 21)
+    want = _expected(case.shared, case.qsizes, case.rsizes, case.k, 5, Q_)
+    assert want[1].tolist() == [5, 5, 0, 5, 5, min(5, int((case.shared[5] > 0).sum()))]
+    # query 0's genome is a prefix of every unmutated copy of its ancestor: full ties, decided by
+    # the index across blocks (its own genome is reference 24)
+    assert want[0]["ref"][0].tolist() == [0, 24, 48, 72, 96] and (want[0]["score"][0] == 1.0).all()
+    try:
+        for blocks in (0, 4):
+            ctx.set_search_batch(blocks)
+            _check(ctx.search_topk(case.Q, case.R, 5, rank=Q_), want)
+    finally:
+        ctx.set_search_batch(0)
 
 
 def _midpoint(values):
