@@ -29,7 +29,8 @@ extern "C" {
                               only): sks_sketch_set_downsample, sks_sketch_set_merge, sks_cluster,
                               sks_cluster_set, sks_gather, sks_gather_sets,
                               sks_ctx_set_gather_rounds, sks_search_topk,
-                              sks_search_topk_sets, sks_sketch_set_filter.  2: deduplicated join layout (masks, region
+                              sks_search_topk_sets, sks_sketch_set_filter,
+                              sks_sketch_set_tally.  2: deduplicated join layout (masks, region
                               ends), elem_words on the layout entry points,
                               sks_ctx_set_join_check; later additions within 2 (new symbols
                               only): sks_ani_rows, sks_intersect_layout_ani, sks_host_alloc,
@@ -291,6 +292,53 @@ typedef enum sks_filter_kind {
 } sks_filter_kind;
 int sks_sketch_set_filter(sks_ctx* ctx, const sks_sketch_set* set, const sks_sketch_set* filters,
                           const uint32_t* filter_of, int kind, sks_sketch_set** out);
+/* Grouped tallies: how many of a group's sketches hold each k-mer.  Sets,
+ * group_off, members and n_groups are exactly as sks_sketch_set_merge takes them
+ * (source sketches numbered in concat order; a sketch may be listed in several
+ * groups or in none; an empty group gives an empty sketch).  A new set of
+ * n_groups sketches on the context's device: with cnt_g(x) the number of listed
+ * members of group g that hold x, sketch g holds the values x with
+ *   max(min_count[g], 1) <= cnt_g(x) <= max_count[g].
+ * A member listed twice counts twice (the rule merge has for windows).  Elements
+ * are ascending (wide ones by the 128-bit value) and unique, whatever the order
+ * of the members.  min 1 and no maximum is the union (sks_sketch_set_merge's
+ * result); min = max = the number of members is the strict core; 1 .. 1 the
+ * k-mers unique to one member; ceil(0.9 m) .. none the 90 % core.
+ *  min_count, max_count: host arrays of n_groups entries.  min_count NULL: 1 for
+ *    every group.  max_count NULL, or an entry UINT32_MAX: no upper limit.  A
+ *    max_count[g] below the effective minimum gives an empty sketch, no error.
+ *  d_counts: NULL, or device memory of counts_cap u32 values.  Entry
+ *    starts[g] + j of it (starts as sks_sketch_set_starts of the result) receives
+ *    cnt_g of element j of sketch g, written by a kernel queued on the context's
+ *    stream.  A counts_cap below the result's total number of elements is
+ *    SKS_E_LENGTH (*out NULL, the contents of d_counts unspecified); the sum of
+ *    the listed members' sizes, over all groups, always suffices.
+ *  Carried over: window, mask, elem_words and the whole policy
+ *    (sks_sketch_set_info of the result equals the sources' but for the number of
+ *    sketches and the names); windows[g] is the sum of the listed members'
+ *    windows.  The result has no names.  No input is modified.
+ *  All sets must be SKS_FRAC_MOD (a bottom-s set is SKS_E_ARG naming "policy
+ *    kind": whether a bottom-s sketch holds a value depends on that sketch's
+ *    other values, so absence from it says nothing) and agree in window, mask,
+ *    elem_words, hash flavour, nonce and policy param (else SKS_E_ARG naming
+ *    "window", "mask", "elem_words", "policy kind", "flavour", "nonce" or "policy
+ *    param"); nothing is downsampled implicitly.
+ * SKS_E_ARG, decided on the host before anything is launched, as
+ * sks_sketch_set_merge words them: a null ctx, sets, out or set (before any
+ * device is touched), n_sets == 0, a null group_off or members where entries are
+ * needed, a group_off that decreases or does not start at 0, a member index >=
+ * the number of source sketches (the message names the index), a set on another
+ * device than the context's.  A group whose members' sizes sum to 2^32 or more
+ * is SKS_E_UNSUPPORTED.  *out is NULL on every failure.
+ * Costs what the merge of the same groups costs: the same rounds, and a last
+ * pass that reads two more elements per distinct value.  Waits for the
+ * context's stream once, to read the new sizes back; the elements and d_counts
+ * are then written by a kernel queued on that stream (sks_ctx_synchronize waits
+ * for it; the source sets may be freed with sks_sketch_set_free at once). */
+int sks_sketch_set_tally(sks_ctx* ctx, const sks_sketch_set* const* sets, uint32_t n_sets,
+                         const uint32_t* group_off, const uint32_t* members, uint32_t n_groups,
+                         const uint32_t* min_count, const uint32_t* max_count,
+                         sks_sketch_set** out, uint32_t* d_counts, uint64_t counts_cap);
 
 /* ---- ordered k-mer lists: nucleotide_string_list_to_kmers (kmer_sliding.cpp:112-238) ---
  * Every selected window of every segment, in stream order, duplicates kept —

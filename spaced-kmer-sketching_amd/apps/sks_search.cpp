@@ -19,6 +19,14 @@
 //       the sketches are found by name across the input databases, the groups
 //       come in order of first appearance and name the output's sketches; the
 //       result equals a database indexed from each group's sequences together
+//   sks-search tally <out.sks> <groups.tsv> <min> <max> <in.sks> [<in.sks> ...]
+//       one sketch per group of groups.tsv (read and named as merge does), the
+//       k-mers held by <min> .. <max> of the sketches the group lists
+//       (sks_sketch_set_tally).  <min> and <max> are each a count (3), a fraction
+//       of the group's listed sketches written with a decimal point (0.9, 1.0:
+//       ceil(f m) as a minimum, at least 1, floor(f m) as a maximum), or - for no
+//       limit.  The 90 % core of every group:   tally out.sks groups.tsv 0.9 - ...
+//       the strict core: 1.0 -;  the k-mers of exactly one sketch: 1 1;  - - is merge
 //   sks-search subtract <db.sks> <filter.sks> <out.sks>
 //   sks-search intersect <db.sks> <filter.sks> <out.sks>
 //       every sketch of the database without (subtract) or within (intersect)
@@ -63,6 +71,7 @@
 #include <vector>
 
 #include "sks.h"
+#include "tally_plan.hpp"
 
 namespace {
 
@@ -102,18 +111,86 @@ sks_sketch_set* sketch_files(sks_ctx* ctx, int n, char* files[], int window, con
   return set;
 }
 
+// merge and tally: the input databases and the groups of groups.tsv (lines
+// group_name<TAB>sketch_name; the sketches are found by name across the inputs,
+// numbered as the library numbers the sources; groups in order of first appearance).
+struct NamedGroups {
+  std::vector<sks_sketch_set*> dbs;
+  std::vector<std::string> names;
+  std::vector<uint32_t> group_off{0}, members;
+};
+
+NamedGroups read_groups(sks_ctx* ctx, const char* tsv_path, int n_dbs, char* db_paths[]) {
+  NamedGroups G;
+  std::map<std::string, uint32_t> index_of;
+  uint32_t n_src = 0;
+  for (int i = 0; i < n_dbs; ++i) {
+    sks_sketch_set* db = nullptr;
+    check(sks_sketch_set_load(ctx, db_paths[i], &db));
+    G.dbs.push_back(db);
+    const uint32_t n = sks_sketch_set_num(db);
+    for (uint32_t k = 0; k < n; ++k) {
+      const char* name = sks_sketch_set_name(db, k);
+      if (!name) throw std::runtime_error(std::string(db_paths[i]) + " has no sketch names");
+      if (!index_of.emplace(name, n_src + k).second)
+        throw std::runtime_error(std::string("sketch name found twice in the inputs: ") + name);
+    }
+    n_src += n;
+  }
+  std::ifstream tsv(tsv_path);
+  if (!tsv) throw std::runtime_error(std::string("cannot read ") + tsv_path);
+  std::map<std::string, size_t> group_of;
+  std::vector<std::vector<uint32_t>> listed;
+  std::string line;
+  while (std::getline(tsv, line)) {
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.empty()) continue;
+    const size_t tab = line.find('\t');
+    if (tab == std::string::npos) throw std::runtime_error("groups line without a tab: " + line);
+    const std::string group = line.substr(0, tab), sketch = line.substr(tab + 1);
+    const auto src = index_of.find(sketch);
+    if (src == index_of.end()) throw std::runtime_error("sketch name not found in the inputs: " + sketch);
+    const auto g = group_of.emplace(group, G.names.size());
+    if (g.second) {
+      G.names.push_back(group);
+      listed.emplace_back();
+    }
+    listed[g.first->second].push_back(src->second);
+  }
+  for (const auto& l : listed) {
+    G.members.insert(G.members.end(), l.begin(), l.end());
+    G.group_off.push_back((uint32_t)G.members.size());
+  }
+  return G;
+}
+
+// Names the grouped result after its groups, saves it, and frees it and the inputs.
+void save_grouped(sks_ctx* ctx, sks_sketch_set* result, const NamedGroups& G, const char* path) {
+  check(sks_ctx_synchronize(ctx));
+  std::vector<const char*> names;
+  for (const std::string& g : G.names) names.push_back(g.c_str());
+  check(sks_sketch_set_set_names(result, names.data()));
+  check(sks_sketch_set_save(result, path));
+  std::printf("%u sketches -> %s\n", sks_sketch_set_num(result), path);
+  sks_sketch_set_free(result);
+  for (sks_sketch_set* db : G.dbs) sks_sketch_set_free(db);
+}
+
 int usage(const char* argv0) {
   std::fprintf(stderr,
                "usage: %s index <out.sks> <w> <k> <c> <fasta files...>\n"
                "       %s query <db.sks> <min_containment> <out.csv> <fasta files...>\n"
                "       %s downsample <in.sks> <c> <out.sks>\n"
                "       %s merge <out.sks> <groups.tsv> <in.sks> [<in.sks> ...]\n"
+               "       %s tally <out.sks> <groups.tsv> <min> <max> <in.sks> [<in.sks> ...]\n"
+               "           (<min>, <max>: a count, a fraction of the group's members written with a\n"
+               "            decimal point, or - for no limit; the 90%% core: tally out groups 0.9 - ...)\n"
                "       %s subtract <db.sks> <filter.sks> <out.sks>\n"
                "       %s intersect <db.sks> <filter.sks> <out.sks>\n"
                "       %s cluster <db.sks> <min_containment> <out.tsv> [<reps.sks>]\n"
                "       %s gather <db.sks> <min_shared> <out.csv> <fasta files...>\n"
                "       %s top <db.sks> <k> <out.csv> <fasta files...>\n",
-               argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0);
+               argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0);
   return 64;
 }
 
@@ -191,60 +268,33 @@ int run(int argc, char* argv[]) {
   }
   if (mode == "merge" && argc >= 5) {
     check(sks_ctx_create(0, nullptr, &ctx));
-    // every input sketch by name, numbered as the library numbers the sources
-    std::vector<sks_sketch_set*> dbs;
-    std::map<std::string, uint32_t> index_of;
-    uint32_t n_src = 0;
-    for (int i = 4; i < argc; ++i) {
-      sks_sketch_set* db = nullptr;
-      check(sks_sketch_set_load(ctx, argv[i], &db));
-      dbs.push_back(db);
-      const uint32_t n = sks_sketch_set_num(db);
-      for (uint32_t k = 0; k < n; ++k) {
-        const char* name = sks_sketch_set_name(db, k);
-        if (!name) throw std::runtime_error(std::string(argv[i]) + " has no sketch names");
-        if (!index_of.emplace(name, n_src + k).second)
-          throw std::runtime_error(std::string("sketch name found twice in the inputs: ") + name);
-      }
-      n_src += n;
-    }
-    std::ifstream tsv(argv[3]);
-    if (!tsv) throw std::runtime_error(std::string("cannot read ") + argv[3]);
-    std::vector<std::string> group_names;
-    std::map<std::string, size_t> group_of;
-    std::vector<std::vector<uint32_t>> listed;
-    std::string line;
-    while (std::getline(tsv, line)) {
-      if (!line.empty() && line.back() == '\r') line.pop_back();
-      if (line.empty()) continue;
-      const size_t tab = line.find('\t');
-      if (tab == std::string::npos) throw std::runtime_error("groups line without a tab: " + line);
-      const std::string group = line.substr(0, tab), sketch = line.substr(tab + 1);
-      const auto src = index_of.find(sketch);
-      if (src == index_of.end()) throw std::runtime_error("sketch name not found in the inputs: " + sketch);
-      const auto g = group_of.emplace(group, group_names.size());
-      if (g.second) {
-        group_names.push_back(group);
-        listed.emplace_back();
-      }
-      listed[g.first->second].push_back(src->second);
-    }
-    std::vector<uint32_t> group_off{0}, members;
-    for (const auto& l : listed) {
-      members.insert(members.end(), l.begin(), l.end());
-      group_off.push_back((uint32_t)members.size());
-    }
+    const NamedGroups G = read_groups(ctx, argv[3], argc - 4, argv + 4);
     sks_sketch_set* merged = nullptr;
-    check(sks_sketch_set_merge(ctx, dbs.data(), (uint32_t)dbs.size(), group_off.data(), members.data(),
-                               (uint32_t)listed.size(), &merged));
-    check(sks_ctx_synchronize(ctx));
-    std::vector<const char*> names;
-    for (const std::string& g : group_names) names.push_back(g.c_str());
-    check(sks_sketch_set_set_names(merged, names.data()));
-    check(sks_sketch_set_save(merged, argv[2]));
-    std::printf("%u sketches -> %s\n", sks_sketch_set_num(merged), argv[2]);
-    sks_sketch_set_free(merged);
-    for (sks_sketch_set* db : dbs) sks_sketch_set_free(db);
+    check(sks_sketch_set_merge(ctx, G.dbs.data(), (uint32_t)G.dbs.size(), G.group_off.data(), G.members.data(),
+                               (uint32_t)G.names.size(), &merged));
+    save_grouped(ctx, merged, G, argv[2]);
+    sks_ctx_destroy(ctx);
+    return 0;
+  }
+  if (mode == "tally" && argc >= 7) {
+    sks::TallyThreshold lo, hi;
+    if (const char* bad = sks::tally_parse_threshold(argv[4], &lo))
+      throw std::runtime_error(std::string("bad <min> '") + argv[4] + "': " + bad);
+    if (const char* bad = sks::tally_parse_threshold(argv[5], &hi))
+      throw std::runtime_error(std::string("bad <max> '") + argv[5] + "': " + bad);
+    check(sks_ctx_create(0, nullptr, &ctx));
+    const NamedGroups G = read_groups(ctx, argv[3], argc - 6, argv + 6);
+    const uint32_t n_groups = (uint32_t)G.names.size();
+    std::vector<uint32_t> min_count(n_groups + 1, 1), max_count(n_groups + 1, UINT32_MAX);
+    for (uint32_t g = 0; g < n_groups; ++g) {
+      const uint32_t m = G.group_off[g + 1] - G.group_off[g];
+      min_count[g] = sks::tally_min_of(lo, m);
+      max_count[g] = sks::tally_max_of(hi, m);
+    }
+    sks_sketch_set* kept = nullptr;
+    check(sks_sketch_set_tally(ctx, G.dbs.data(), (uint32_t)G.dbs.size(), G.group_off.data(), G.members.data(),
+                               n_groups, min_count.data(), max_count.data(), &kept, nullptr, 0));
+    save_grouped(ctx, kept, G, argv[2]);
     sks_ctx_destroy(ctx);
     return 0;
   }

@@ -19,6 +19,7 @@
 #include "code_objects.hpp"
 #include "downsample.hpp"
 #include "merge.hpp"
+#include "merge_device.hpp"
 
 namespace sks {
 
@@ -26,27 +27,7 @@ SKS_CODE_OBJECT_HOOK(merge)
 
 namespace {
 
-constexpr int kMgB = 256;
-constexpr int kMgWaves = kMgB / 64;
-constexpr int kMgItems = (int)kMergeTile / kMgB;
-static_assert(kMgItems * kMgB == (int)kMergeTile, "a tile is a whole number of block strides");
 static_assert(kMergeTile == kDownsampleChunk, "the duplicate filter's chunks are counted by downsample_offsets");
-
-// One element: a u64 (narrow) or a 16-byte (lo, hi) pair ordered hi word major (wide).
-template <int EW>
-struct MElem;
-template <>
-struct MElem<1> {
-  using type = uint64_t;
-  static __device__ __forceinline__ bool less(type x, type y) { return x < y; }
-  static __device__ __forceinline__ bool same(type x, type y) { return x == y; }
-};
-template <>
-struct MElem<2> {
-  using type = ulong2;
-  static __device__ __forceinline__ bool less(type x, type y) { return x.y < y.y || (x.y == y.y && x.x < y.x); }
-  static __device__ __forceinline__ bool same(type x, type y) { return x.x == y.x && x.y == y.y; }
-};
 
 template <int EW>
 struct Reader {
@@ -107,22 +88,12 @@ __global__ __launch_bounds__(kMgB) void k_merge_round(const uint64_t* __restrict
   for (uint32_t t = threadIdx.x; t < m; t += kMgB) out[(uint64_t)d0 + t] = tile[t];
 }
 
-// The chunk of this workgroup: group g's elements src[0 .. size), the chunk from `base`.
+// An element stays iff it is the first of its value in its group.
 template <int EW>
-struct GroupChunk {
-  const typename MElem<EW>::type* src;
-  uint64_t size, base;
-  __device__ __forceinline__ void open(const uint64_t* runs, const uint64_t* chunk_off, uint32_t n_groups) {
-    const uint32_t g = tile_owner(chunk_off, n_groups, blockIdx.x);
-    src = reinterpret_cast<const typename MElem<EW>::type*>(runs[2 * (uint64_t)g]);
-    size = runs[2 * (uint64_t)g + 1];
-    base = (blockIdx.x - chunk_off[g]) * kMergeTile;
-  }
-  // element i and whether it stays (the first of its value)
-  __device__ __forceinline__ bool first_of_value(uint64_t i, typename MElem<EW>::type& v) const {
-    if (i >= size) return false;
-    v = src[i];
-    return i == 0 || !MElem<EW>::same(v, src[i - 1]);
+struct FirstOfValue {
+  GroupChunk<EW> ch;
+  __device__ __forceinline__ bool operator()(uint64_t i, typename MElem<EW>::type& v) const {
+    return ch.first_of_value(i, v);
   }
 };
 
@@ -130,25 +101,10 @@ template <int EW>
 __global__ __launch_bounds__(kMgB) void k_mu_count(const uint64_t* __restrict__ runs,
                                                    const uint64_t* __restrict__ chunk_off, uint32_t n_groups,
                                                    uint32_t* __restrict__ counts) {
-  using T = typename MElem<EW>::type;
   __shared__ uint32_t wsum[kMgWaves];
-  GroupChunk<EW> ch;
-  ch.open(runs, chunk_off, n_groups);
-  uint32_t cnt = 0;  // of this wave
-#pragma unroll
-  for (int j = 0; j < kMgItems; ++j) {
-    T v{};
-    const bool p = ch.first_of_value(ch.base + (uint64_t)j * kMgB + threadIdx.x, v);
-    cnt += (uint32_t)__popcll(__ballot(p));
-  }
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t all = 0;
-#pragma unroll
-    for (int w = 0; w < kMgWaves; ++w) all += wsum[w];
-    counts[blockIdx.x] = all;
-  }
+  FirstOfValue<EW> keep;
+  keep.ch.open(runs, chunk_off, n_groups);
+  chunk_count<EW>(keep.ch.base, keep, wsum, counts);
 }
 
 template <int EW>
@@ -157,37 +113,12 @@ __global__ __launch_bounds__(kMgB) void k_mu_scatter(const uint64_t* __restrict_
                                                      const uint64_t* __restrict__ offs,
                                                      uint64_t* __restrict__ out_words) {
   using T = typename MElem<EW>::type;
-  __shared__ uint32_t wsum[kMgItems * kMgWaves];  // kept per (stride j, wave), in element order
-  GroupChunk<EW> ch;
-  ch.open(runs, chunk_off, n_groups);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  T v[kMgItems];
-  bool p[kMgItems];
-  uint32_t in_wave[kMgItems];
-#pragma unroll
-  for (int j = 0; j < kMgItems; ++j) {
-    v[j] = T{};
-    p[j] = ch.first_of_value(ch.base + (uint64_t)j * kMgB + threadIdx.x, v[j]);
-    const uint64_t bal = __ballot(p[j]);
-    in_wave[j] = (uint32_t)__popcll(bal & ((1ull << lane) - 1));
-    if (lane == 0) wsum[j * kMgWaves + wave] = (uint32_t)__popcll(bal);
-  }
-  __syncthreads();
+  __shared__ uint32_t wsum[kMgItems * kMgWaves];
+  FirstOfValue<EW> keep;
+  keep.ch.open(runs, chunk_off, n_groups);
   T* out = reinterpret_cast<T*>(out_words) + offs[blockIdx.x];
-  uint32_t run = 0;
-#pragma unroll
-  for (int j = 0; j < kMgItems; ++j) {
-    uint32_t before = 0;
-#pragma unroll
-    for (int w = 0; w < kMgWaves; ++w) {
-      if (w == wave) before = run;
-      run += wsum[j * kMgWaves + w];
-    }
-    if (p[j]) out[before + in_wave[j]] = v[j];
-  }
+  chunk_scatter<EW>(keep.ch.base, keep, wsum, [out](uint32_t rank, uint64_t, T v) { out[rank] = v; });
 }
-
-constexpr uint64_t kMgMaxGrid = 0x7fffffffull;
 
 }  // namespace
 

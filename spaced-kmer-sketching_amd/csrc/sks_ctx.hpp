@@ -1,7 +1,8 @@
 // What the C-ABI translation units that run on a device share (ctx.cpp,
 // host_mem.cpp, sketch_set.cpp, kmer_list.cpp, build.cpp, build_post.cpp,
 // pairs.cpp, search_api.cpp, topk_api.cpp, cluster_api.cpp, gather_api.cpp,
-// downsample_api.cpp, merge_api.cpp, filter_api.cpp): the context, the sketch set and k-mer
+// downsample_api.cpp, merge_rounds.cpp, merge_api.cpp, tally_api.cpp, filter_api.cpp): the
+// context, the sketch set and k-mer
 // list with the device blocks they own, the error macros, the metadata arena,
 // SketchSpan and the group bounds of the set-level calls (their device-free
 // rules: set_rules.hpp) and small argument helpers.
@@ -33,6 +34,7 @@
 #include "set_rules.hpp"
 #include "sks.h"
 #include "sks_api_internal.hpp"
+#include "tally.hpp"
 #include "topk.hpp"
 #include "windows.hpp"
 
@@ -299,6 +301,40 @@ inline uint64_t* chunk_offs(sks_ctx* c) { return reinterpret_cast<uint64_t*>(c->
 int reserve_chunk_counters(sks_ctx* c, uint64_t n_chunks);
 int size_set_from_counts(sks_ctx* c, const char* who, const char* too_large, uint64_t n_chunks,
                          const uint64_t* d_chunk_off, const uint32_t* bound, sks_sketch_set* set);
+
+// ---- groups of source sketches and their merge rounds (merge_rounds.cpp) ----------------
+// What sks_sketch_set_merge and sks_sketch_set_tally share.  group_sources is
+// their argument check, refusing as "<who>: ..." (null ctx, sets or out before
+// anything else; no sets; a null set; a set on another device or differing from
+// set 0, ParamRule::kFracOnly; with `frac_only`, that text for sets that are not
+// FracMinHash; unknown kind or flavour; elem_words; bottom-s param 0; group_off
+// and member indices; SKS_E_UNSUPPORTED for a group of 2^32 or more elements),
+// and the source sketches it leaves, numbered as sks_sketch_set_concat orders them.
+struct GroupSources {
+  int ew = 1;
+  sks_policy policy{};               // set 0's; bottom-s: the smallest param
+  uint32_t n_groups = 0, n_members = 0;
+  const uint32_t* members = nullptr;  // the caller's
+  std::vector<uint64_t> src_addr;     // [source sketches] device address of the first element
+  std::vector<uint32_t> goff;         // [n_groups + 1]
+  std::vector<uint32_t> member_len;   // [n_members] elements of each listed member
+  std::vector<uint64_t> windows;      // [n_groups] sum of the listed members' windows
+};
+int group_sources(const char* who, const sks_ctx* c, const sks_sketch_set* const* sets, uint32_t n_sets,
+                  const uint32_t* group_off, const uint32_t* members, uint32_t n_groups, const void* out,
+                  const char* frac_only, GroupSources* S);
+// queue_group_rounds plans the pairwise rounds (merge_plan.hpp), uploads their
+// run tables, the final `runs` and `chunk_off` tables and the caller's `extra`
+// table (may be null) in one arena, reserves the two scratch columns and the
+// chunk counters and queues every round on the context's stream (its device
+// current).  Afterwards group g is one sorted run, duplicates kept, of
+// run_len[g] elements at d_runs[2g]; the last pass is the caller's.
+struct GroupRuns {
+  const uint64_t *d_runs = nullptr, *d_chunk_off = nullptr, *d_extra = nullptr;
+  uint64_t n_chunks = 0;
+  std::vector<uint32_t> run_len;  // [n_groups]; each fits 32 bits (group_sources)
+};
+int queue_group_rounds(sks_ctx* c, const GroupSources& S, const std::vector<uint64_t>* extra, GroupRuns* R);
 
 // ---- argument helpers (ctx.cpp) ---------------------------------------------------------
 // The opening checks of the entry points that take a join layout: a context, a

@@ -6,6 +6,7 @@ or a GPU is missing, the calls below raise.  Device buffers are torch tensors
 on `cuda:N` whose data_ptr() is handed to the C ABI.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -17,6 +18,7 @@ SKS_FRAC_MOD = 0
 SKS_BOTTOM_S = 1
 SKS_FILTER_SUBTRACT, SKS_FILTER_INTERSECT = 0, 1  # sks_filter_kind
 FILTER_NONE = 0xFFFFFFFF  # a filter_of entry: the sketch is copied unchanged
+TALLY_NO_LIMIT = 0xFFFFFFFF  # a max_count entry of Context.tally: no upper limit
 INTERSECT_AUTO, INTERSECT_MERGE, INTERSECT_JOIN, INTERSECT_GLOBAL = 0, 1, 2, 3
 FRAC_POST_AUTO, FRAC_POST_GENERAL, FRAC_POST_FUSED = 0, 1, 2
 BUILD_PATH_GENERAL, BUILD_PATH_FUSED, BUILD_PATH_FUSED_THEN_GENERAL_POST = 0, 1, 2
@@ -79,7 +81,7 @@ EXPORTED = [
     "sks_search", "sks_search_sets", "sks_ctx_set_search_batch", "sks_sketch_set_downsample",
     "sks_sketch_set_merge", "sks_cluster", "sks_cluster_set",
     "sks_gather", "sks_gather_sets", "sks_ctx_set_gather_rounds",
-    "sks_search_topk", "sks_search_topk_sets", "sks_sketch_set_filter",
+    "sks_search_topk", "sks_search_topk_sets", "sks_sketch_set_filter", "sks_sketch_set_tally",
     "sks_join_layout_region_log", "sks_join_launch_plan",
 ]
 
@@ -213,6 +215,8 @@ def lib():
     L.sks_sketch_set_downsample.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp)]
     L.sks_sketch_set_merge.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(vp)]
     L.sks_sketch_set_filter.argtypes = [vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
+    L.sks_sketch_set_tally.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.POINTER(vp), vp,
+                                       C.c_uint64]
     L.sks_kmer_list_build.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, u64p,
                                       C.POINTER(Policy), C.POINTER(vp)]
     L.sks_windows_dense.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, u64p, vp, vp]
@@ -704,6 +708,55 @@ class Context:
         check(lib().sks_sketch_set_merge(self.h, arr, len(sets), off.ctypes.data, mem.ctypes.data, len(groups),
                                          C.byref(h)))
         return SketchSet(h)
+
+    def tally(self, sets, groups, min_count=None, max_count=None, counts=False):
+        """sks_sketch_set_tally: one sketch per entry of `groups` (as merge takes
+        them), holding the values that min_count .. max_count of the group's listed
+        members hold.  min_count / max_count: None (1 / no limit), one integer for
+        every group, or one value per group; TALLY_NO_LIMIT as a max is no limit.
+        counts=True: returns (set, counts), counts a host u32 array in the set's
+        flat order (entry starts[g] + j: the members holding element j of sketch g)."""
+        arr = (C.c_void_p * len(sets))(*[s.h for s in sets])
+        off = np.zeros(len(groups) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(g) for g in groups], dtype=np.int64)
+        mem = np.array([i for g in groups for i in g] + [0], dtype=np.uint32)
+
+        def per_group(v, what):
+            if v is None:
+                return None
+            a = np.full(len(groups), v, dtype=np.uint32) if np.isscalar(v) else np.array(list(v), dtype=np.uint32)
+            if len(a) != len(groups):
+                raise ValueError(f"{what} has {len(a)} entries for {len(groups)} groups")
+            return np.append(a, np.uint32(0))  # never empty
+
+        lo, hi = per_group(min_count, "min_count"), per_group(max_count, "max_count")
+        buf, cap = None, 0
+        if counts:
+            import torch
+            src = np.concatenate([s.sizes() for s in sets]) if sets else np.zeros(0, np.uint32)
+            cap = int(sum(int(src[i]) for g in groups for i in g if i < len(src)))  # always suffices
+            buf = torch.zeros(max(cap, 1), dtype=torch.int32, device=torch.device("cuda", self.device))
+        h = C.c_void_p()
+        check(lib().sks_sketch_set_tally(self.h, arr, len(sets), off.ctypes.data, mem.ctypes.data, len(groups),
+                                         None if lo is None else lo.ctypes.data,
+                                         None if hi is None else hi.ctypes.data, C.byref(h),
+                                         None if buf is None else C.c_void_p(buf.data_ptr()), cap))
+        out = SketchSet(h)
+        if not counts:
+            return out
+        self.synchronize()
+        total = int(out.sizes().sum()) if out.n else 0
+        return out, buf.cpu().numpy().view(np.uint32)[:total].copy()
+
+    def core(self, sets, groups, min_fraction):
+        """The k-mers held by at least min_fraction of each group's listed members:
+        tally with min_count = max(1, ceil(min_fraction * members)), the fraction
+        taken as the decimal it prints as (0.9 of 10 is 9)."""
+        from fractions import Fraction
+        f = Fraction(str(min_fraction))
+        if not 0 <= f <= 1:
+            raise ValueError(f"min_fraction {min_fraction} is not within 0 .. 1")
+        return self.tally(sets, groups, min_count=[max(1, math.ceil(f * len(g))) for g in groups])
 
     def filter(self, sketch_set, filters, kind, filter_of=None):
         """sks_sketch_set_filter: sketch i of the result holds the elements of sketch i
