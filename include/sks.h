@@ -30,7 +30,10 @@ extern "C" {
                               sks_cluster_set, sks_gather, sks_gather_sets,
                               sks_ctx_set_gather_rounds, sks_search_topk,
                               sks_search_topk_sets, sks_sketch_set_filter,
-                              sks_sketch_set_tally.  2: deduplicated join layout (masks, region
+                              sks_sketch_set_tally, sks_sketch_build_counted,
+                              sks_sketch_set_has_abund, sks_sketch_set_device_abund,
+                              sks_sketch_set_abund_copy, sks_sketch_set_abund_totals,
+                              sks_sketch_set_abund_trim, sks_abund_pairs.  2: deduplicated join layout (masks, region
                               ends), elem_words on the layout entry points,
                               sks_ctx_set_join_check; later additions within 2 (new symbols
                               only): sks_ani_rows, sks_intersect_layout_ani, sks_host_alloc,
@@ -196,11 +199,16 @@ int sks_sketch_set_info(const sks_sketch_set* set, sks_sketch_info* info);
 int sks_sketch_set_set_names(sks_sketch_set* set, const char* const* names);
 /* Name of sketch i, or NULL when the set has no names. */
 const char* sks_sketch_set_name(const sks_sketch_set* set, uint32_t i);
+/* A set with abundances (below) is written as file version 3, its abundances
+ * between the elements and the names; any other set as version 1, byte for byte
+ * as before version 3 existed.  Load reads both; a version-3 file with a zero
+ * abundance, a short section or a bad checksum is SKS_E_IO. */
 int sks_sketch_set_save(const sks_sketch_set* set, const char* path);
 int sks_sketch_set_load(sks_ctx* ctx, const char* path, sks_sketch_set** out);
 /* One set holding the sketches of sets[0], sets[1], ... in order (e.g. shards
  * sketched on different ranks or at different times).  All sets must share
- * window, mask and policy. */
+ * window, mask and policy.  Abundances are carried when all sets have them; sets
+ * of which only some have them are SKS_E_ARG naming "abundance". */
 int sks_sketch_set_concat(sks_ctx* ctx, const sks_sketch_set* const* sets, uint32_t n_sets,
                           sks_sketch_set** out);
 /* A coarser copy of `set` on the context's device, identical to what
@@ -339,6 +347,64 @@ int sks_sketch_set_tally(sks_ctx* ctx, const sks_sketch_set* const* sets, uint32
                          const uint32_t* group_off, const uint32_t* members, uint32_t n_groups,
                          const uint32_t* min_count, const uint32_t* max_count,
                          sks_sketch_set** out, uint32_t* d_counts, uint64_t counts_cap);
+
+/* ---- k-mer abundances: counted sketch sets ---------------------------------------------
+ * A sketch set may carry one more column, the abundance of every element: how
+ * often its k-mer was selected in the sequence the sketch was built from.  Only
+ * sks_sketch_build_counted, sks_sketch_set_abund_trim, sks_sketch_set_load (of a
+ * counted set's file) and sks_sketch_set_concat (of counted sets) return a set
+ * with abundances.  Every other call takes a counted set as it takes any set:
+ * its results are those of the set without the column, and a set it returns
+ * (downsample, merge, filter, tally) has no abundances.
+ *
+ * sks_sketch_build that also counts.  abund(x, g) = the number of selected windows of segment g
+ * whose canonical masked k-mer is x, i.e. x's multiplicity in sks_kmer_list_build's list of
+ * segment g.  Sketch g keeps x iff max(min_abund, 1) <= abund(x, g) <= max_abund
+ * (max_abund == UINT32_MAX: no limit; max_abund below the minimum: empty sketches, no error).
+ * Counts are clamped to UINT32_MAX.  SKS_FRAC_MOD only: SKS_BOTTOM_S is SKS_E_UNSUPPORTED
+ * naming "policy kind".  With min_abund <= 1 and no limit, the elements, sizes, starts and
+ * windows are bit for bit those of sks_sketch_build.  windows[g] never depends on the limits.
+ * Every other argument, check and message as sks_sketch_build.  sks_ctx_last_timings filled
+ * as for a build; sks_ctx_last_build_path is SKS_BUILD_PATH_GENERAL. */
+int sks_sketch_build_counted(sks_ctx* ctx, const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* seg_off,
+                             uint32_t n_seg, int window, const uint64_t mask[2], const sks_policy* policy,
+                             uint32_t min_abund, uint32_t max_abund, sks_sketch_set** out);
+
+int sks_sketch_set_has_abund(const sks_sketch_set* set);                 /* 1 / 0 (0 for NULL) */
+/* u32[total], entry starts[i] + j = abundance (>= 1) of element j of sketch i; NULL when none */
+const uint32_t* sks_sketch_set_device_abund(const sks_sketch_set* set);
+/* sizes[i] values to the host (SKS_E_ARG naming "abundance" for a set without them) */
+int sks_sketch_set_abund_copy(const sks_sketch_set* set, uint32_t i, uint32_t* out);
+/* totals[i] = the sum of sketch i's abundances (u64), n host values; waits for the device.
+ * SKS_E_ARG naming "abundance" for a set without them. */
+int sks_sketch_set_abund_totals(const sks_sketch_set* set, uint64_t* totals);
+
+/* A new counted set: the elements of `set` (which must have abundances, else SKS_E_ARG naming
+ * "abundance") with max(min_abund,1) <= abundance <= max_abund, order kept, abundances carried.
+ * Window, mask, policy, windows and names carried over, as sks_sketch_set_filter does.
+ * Identity: build_counted(.., lo, hi) == trim(build_counted(.., 1, UINT32_MAX), lo, hi).
+ * SKS_E_ARG, decided on the host before any device is touched: a null ctx, set or out, a set
+ * on another device than the context's.  *out is NULL on every failure.  Waits for the
+ * context's stream once, to read the new sizes back; the elements and abundances are then
+ * written by a kernel queued on that stream. */
+int sks_sketch_set_abund_trim(sks_ctx* ctx, const sks_sketch_set* set, uint32_t min_abund, uint32_t max_abund,
+                              sks_sketch_set** out);
+
+/* Weighted overlap of n_pairs sketch pairs.  For pair p, with A = sketch d_a[p] of `samples` and
+ * B = sketch d_b[p] of `refs`: d_shared[p] = |A ∩ B| and
+ * d_weight[p] = sum of A's abundances over A ∩ B (u64).  d_a / d_b / outputs are device arrays,
+ * queued on the context's stream, no host wait.  `samples` must have abundances.  `refs` need not,
+ * and refs' own abundances are ignored.  refs == samples is allowed.  Compatibility: the checks
+ * and messages of sks_gather_sets (both SKS_FRAC_MOD, same window, mask, elem_words, flavour,
+ * nonce and policy param).  An index >= the set's number of sketches (or below 0) cannot be
+ * seen by the host: the kernel writes shared = -1, weight = 0 for that pair and reads nothing.
+ * weight / shared is the mean depth of the shared k-mers.  weight / totals[a] is the share of
+ * the sample's k-mer mass inside the reference.  The result does not depend on the order in
+ * which the device runs the pairs (no atomics).
+ * SKS_E_ARG, decided on the host before any device is touched: a null ctx or set, n_pairs > 0
+ * with a null array, a set on another device than the context's. */
+int sks_abund_pairs(sks_ctx* ctx, const sks_sketch_set* samples, const sks_sketch_set* refs, const int32_t* d_a,
+                    const int32_t* d_b, uint64_t n_pairs, int32_t* d_shared, uint64_t* d_weight);
 
 /* ---- ordered k-mer lists: nucleotide_string_list_to_kmers (kmer_sliding.cpp:112-238) ---
  * Every selected window of every segment, in stream order, duplicates kept —

@@ -4,6 +4,17 @@
 //   sks-search index <out.sks> <w> <k> <c> <a.fa> <b.fa> ...
 //       one FracMinHash sketch (1/c) per FASTA file under the seed-0 spaced mask
 //       of (w, k), stored with the file names (sks_sketch_set_save)
+//   sks-search index-abund <out.sks> <w> <k> <c> <min> <max|-> <a.fa> <b.fa> ...
+//       as index, but counted (sks_sketch_build_counted): every kept k-mer with
+//       the number of times it was selected in its file, and only the k-mers
+//       selected <min> .. <max> times (- for no maximum; min 2 drops the k-mers
+//       seen once, the sequencing errors of raw reads)
+//   sks-search weigh <sample.sks> <db.sks> <min_containment> <out.csv>
+//       the pairs query finds between the sketches of a counted database
+//       (index-abund) and a reference database (sks_search_sets), each with the
+//       sample's abundances over the shared k-mers (sks_abund_pairs):
+//         Query,Reference,Shared,Containment,ANI,Weight,MeanDepth,FWeighted   (doubles as %.17g)
+//       MeanDepth = Weight / Shared, FWeighted = Weight / the sum of the query's abundances
 //   sks-search query <db.sks> <min_containment> <out.csv> <q.fa> ...
 //       sketches the queries with the database's window, mask and policy and
 //       writes every (query, reference) pair whose containment of the query is
@@ -85,8 +96,9 @@ void check_hip(hipError_t e, const char* what) {
 
 // One sketch per file: the files' record streams back to back in device memory,
 // a segment per file, one build; the file names become the sketch names.
+// With `limits` = {min, max} the build also counts (sks_sketch_build_counted).
 sks_sketch_set* sketch_files(sks_ctx* ctx, int n, char* files[], int window, const uint64_t mask[2],
-                             const sks_policy& policy) {
+                             const sks_policy& policy, const uint32_t* limits = nullptr) {
   std::vector<uint8_t> stream;
   std::vector<uint64_t> seg_off{0};
   for (int i = 0; i < n; ++i) {
@@ -101,8 +113,11 @@ sks_sketch_set* sketch_files(sks_ctx* ctx, int n, char* files[], int window, con
   check_hip(hipMalloc(&d_seq, stream.size() ? stream.size() : 1), "hipMalloc");
   if (!stream.empty()) check_hip(hipMemcpy(d_seq, stream.data(), stream.size(), hipMemcpyHostToDevice), "hipMemcpy");
   sks_sketch_set* set = nullptr;
-  const int rc = sks_sketch_build(ctx, static_cast<const uint8_t*>(d_seq), stream.size(), seg_off.data(),
-                                  (uint32_t)n, window, mask, &policy, &set);
+  const int rc = limits ? sks_sketch_build_counted(ctx, static_cast<const uint8_t*>(d_seq), stream.size(),
+                                                   seg_off.data(), (uint32_t)n, window, mask, &policy, limits[0],
+                                                   limits[1], &set)
+                        : sks_sketch_build(ctx, static_cast<const uint8_t*>(d_seq), stream.size(), seg_off.data(),
+                                           (uint32_t)n, window, mask, &policy, &set);
   if (rc == SKS_OK) (void)sks_ctx_synchronize(ctx);
   (void)hipFree(d_seq);
   check(rc);
@@ -179,6 +194,8 @@ void save_grouped(sks_ctx* ctx, sks_sketch_set* result, const NamedGroups& G, co
 int usage(const char* argv0) {
   std::fprintf(stderr,
                "usage: %s index <out.sks> <w> <k> <c> <fasta files...>\n"
+               "       %s index-abund <out.sks> <w> <k> <c> <min> <max|-> <fasta files...>\n"
+               "       %s weigh <sample.sks> <db.sks> <min_containment> <out.csv>\n"
                "       %s query <db.sks> <min_containment> <out.csv> <fasta files...>\n"
                "       %s downsample <in.sks> <c> <out.sks>\n"
                "       %s merge <out.sks> <groups.tsv> <in.sks> [<in.sks> ...]\n"
@@ -190,7 +207,7 @@ int usage(const char* argv0) {
                "       %s cluster <db.sks> <min_containment> <out.tsv> [<reps.sks>]\n"
                "       %s gather <db.sks> <min_shared> <out.csv> <fasta files...>\n"
                "       %s top <db.sks> <k> <out.csv> <fasta files...>\n",
-               argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0);
+               argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0);
   return 64;
 }
 
@@ -208,6 +225,94 @@ int run(int argc, char* argv[]) {
     check(sks_sketch_set_save(set, argv[2]));
     std::printf("%u sketches -> %s\n", sks_sketch_set_num(set), argv[2]);
     sks_sketch_set_free(set);
+    sks_ctx_destroy(ctx);
+    return 0;
+  }
+  if (mode == "index-abund" && argc >= 9) {
+    const int w = std::atoi(argv[3]), k = std::atoi(argv[4]);
+    const uint64_t c = std::strtoull(argv[5], nullptr, 10);
+    uint32_t limits[2] = {1, UINT32_MAX};
+    for (int i = 0; i < 2; ++i) {
+      const char* text = argv[6 + i];
+      if (i == 1 && std::strcmp(text, "-") == 0) continue;
+      char* end = nullptr;
+      const unsigned long long v = std::strtoull(text, &end, 10);
+      if (end == text || *end || text[0] == '-' || v > UINT32_MAX)
+        throw std::runtime_error(std::string(i ? "bad <max>: " : "bad <min>: ") + text);
+      limits[i] = (uint32_t)v;
+    }
+    uint64_t mask[2];
+    check(sks_mask_generate(w, k, 0, mask));
+    check(sks_ctx_create(0, nullptr, &ctx));
+    const sks_policy policy{SKS_FRAC_MOD, SKS_HASH_BOOST_MIX, c, 1};
+    sks_sketch_set* set = sketch_files(ctx, argc - 8, argv + 8, w, mask, policy, limits);
+    check(sks_sketch_set_save(set, argv[2]));
+    std::printf("%u sketches -> %s\n", sks_sketch_set_num(set), argv[2]);
+    sks_sketch_set_free(set);
+    sks_ctx_destroy(ctx);
+    return 0;
+  }
+  if (mode == "weigh" && argc == 6) {
+    char* end = nullptr;
+    const double min_containment = std::strtod(argv[4], &end);
+    if (end == argv[4] || *end) throw std::runtime_error(std::string("bad min_containment: ") + argv[4]);
+    check(sks_ctx_create(0, nullptr, &ctx));
+    sks_sketch_set *sample = nullptr, *db = nullptr;
+    check(sks_sketch_set_load(ctx, argv[2], &sample));
+    check(sks_sketch_set_load(ctx, argv[3], &db));
+    // refused here, with the library's message, for a sample without abundances
+    check(sks_abund_pairs(ctx, sample, db, nullptr, nullptr, 0, nullptr, nullptr));
+    std::vector<uint64_t> totals(sks_sketch_set_num(sample));
+    check(sks_sketch_set_abund_totals(sample, totals.data()));
+    uint64_t n = 0;
+    check(sks_search_sets(ctx, sample, db, min_containment, 1, nullptr, 0, &n));
+    std::vector<sks_hit> hits(n);
+    std::vector<int32_t> shared(n);
+    std::vector<uint64_t> weight(n);
+    if (n) {
+      void *d_hits = nullptr, *d_idx = nullptr, *d_shared = nullptr, *d_weight = nullptr;
+      check_hip(hipMalloc(&d_hits, n * sizeof(sks_hit)), "hipMalloc");
+      check_hip(hipMalloc(&d_idx, 2 * n * sizeof(int32_t)), "hipMalloc");
+      check_hip(hipMalloc(&d_shared, n * sizeof(int32_t)), "hipMalloc");
+      check_hip(hipMalloc(&d_weight, n * sizeof(uint64_t)), "hipMalloc");
+      int rc = sks_search_sets(ctx, sample, db, min_containment, 1, static_cast<sks_hit*>(d_hits), n, &n);
+      if (rc == SKS_OK) rc = sks_ctx_synchronize(ctx);
+      if (rc == SKS_OK) {
+        check_hip(hipMemcpy(hits.data(), d_hits, n * sizeof(sks_hit), hipMemcpyDeviceToHost), "hipMemcpy");
+        std::vector<int32_t> idx(2 * n);
+        for (uint64_t i = 0; i < n; ++i) {
+          idx[i] = (int32_t)hits[i].query;
+          idx[n + i] = (int32_t)hits[i].ref;
+        }
+        check_hip(hipMemcpy(d_idx, idx.data(), 2 * n * sizeof(int32_t), hipMemcpyHostToDevice), "hipMemcpy");
+        rc = sks_abund_pairs(ctx, sample, db, static_cast<const int32_t*>(d_idx),
+                             static_cast<const int32_t*>(d_idx) + n, n, static_cast<int32_t*>(d_shared),
+                             static_cast<uint64_t*>(d_weight));
+        if (rc == SKS_OK) rc = sks_ctx_synchronize(ctx);
+        if (rc == SKS_OK) {
+          check_hip(hipMemcpy(shared.data(), d_shared, n * sizeof(int32_t), hipMemcpyDeviceToHost), "hipMemcpy");
+          check_hip(hipMemcpy(weight.data(), d_weight, n * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy");
+        }
+      }
+      for (void* p : {d_hits, d_idx, d_shared, d_weight}) (void)hipFree(p);
+      check(rc);
+    }
+    FILE* out = std::fopen(argv[5], "w");
+    if (!out) throw std::runtime_error(std::string("cannot write ") + argv[5]);
+    std::fprintf(out, "Query,Reference,Shared,Containment,ANI,Weight,MeanDepth,FWeighted\n");
+    for (uint64_t i = 0; i < n; ++i) {
+      const sks_hit& h = hits[i];
+      if (shared[i] != h.shared) throw std::runtime_error("the weighted overlap and the search disagree on a pair");
+      const char *qn = sks_sketch_set_name(sample, h.query), *rn = sks_sketch_set_name(db, h.ref);
+      const std::string q_name = qn ? qn : std::to_string(h.query), r_name = rn ? rn : std::to_string(h.ref);
+      std::fprintf(out, "%s,%s,%d,%.17g,%.17g,%llu,%.17g,%.17g\n", q_name.c_str(), r_name.c_str(), h.shared,
+                   h.containment, h.ani, (unsigned long long)weight[i], (double)weight[i] / (double)h.shared,
+                   (double)weight[i] / (double)totals[h.query]);
+    }
+    std::fclose(out);
+    std::printf("%llu hits -> %s\n", (unsigned long long)n, argv[5]);
+    sks_sketch_set_free(sample);
+    sks_sketch_set_free(db);
     sks_ctx_destroy(ctx);
     return 0;
   }

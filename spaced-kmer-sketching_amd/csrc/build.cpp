@@ -331,8 +331,11 @@ int assemble_set(BuildState& S, uint32_t n_seg, Passes& P, SetPtr* out) {
                                std::is_sorted(P.out[0].segs.begin(), P.out[0].segs.end());
   const uint64_t mask[2] = {S.mask_lo, S.mask_hi}, words = total * S.ew;
   SetPtr set;
+  DevBlock abund;  // a counted build: placed as the elements are
+  if (S.counted && !single_in_order) SKS_HIP(abund.alloc(std::max<uint64_t>(total, 1) * sizeof(uint32_t), st));
   SKS_TRY(make_sketch_set(c->device, S.ew, S.w, mask, S.pol, std::move(sizes), P.windows, {},
-                          single_in_order ? nullptr : &words, st, MetaUpload::kStream, &set));
+                          single_in_order ? nullptr : &words, st, MetaUpload::kStream, &set,
+                          S.counted ? (single_in_order ? &P.out[0].abund : &abund) : nullptr));
   if (single_in_order) set->data = std::move(P.out[0].d);
   for (const PassOut& po : P.out) {
     if (single_in_order) break;
@@ -342,11 +345,17 @@ int assemble_set(BuildState& S, uint32_t n_seg, Passes& P, SetPtr* out) {
       if (len)
         SKS_HIP(hipMemcpyAsync(set->d_data() + set->starts[po.segs[i]] * S.ew, po.d.as<uint64_t>() + po.off[i] * S.ew,
                                len * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+      if (len && S.counted)
+        SKS_HIP(hipMemcpyAsync(set->d_abund() + set->starts[po.segs[i]], po.abund.as<uint32_t>() + po.off[i],
+                               (po.off[i + 1] - po.off[i]) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     }
   }
   SKS_HIP(hipEventRecord(c->ev_end, st));
   SKS_HIP(hipStreamSynchronize(st));
-  for (PassOut& po : P.out) po.d.release();
+  for (PassOut& po : P.out) {
+    po.d.release();
+    po.abund.release();
+  }
   *out = std::move(set);
   return SKS_OK;
 }
@@ -406,6 +415,45 @@ extern "C" int sks_sketch_build(sks_ctx* c, const uint8_t* d_seq, uint64_t n_byt
     }
   }
 
+  SKS_TRY(run_passes(S, d_seq, seg_off, n_seg, P, tm));
+  SetPtr set;
+  SKS_TRY(assemble_set(S, n_seg, P, &set));
+  float tot = 0;
+  (void)hipEventElapsedTime(&tot, c->ev_begin, c->ev_end);
+  tm.total_ms = tot;
+  tm.post_ms = tot - tm.scan_ms;
+  for (uint64_t wv : P.windows) tm.windows += wv;
+  c->last = tm;
+  *out = set.release();
+  return SKS_OK;
+}
+
+extern "C" int sks_sketch_build_counted(sks_ctx* c, const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* seg_off,
+                                        uint32_t n_seg, int window, const uint64_t mask[2], const sks_policy* policy,
+                                        uint32_t min_abund, uint32_t max_abund, sks_sketch_set** out) {
+  if (!out) return sks::fail(SKS_E_ARG, "sks_sketch_build_counted: null argument");
+  *out = nullptr;
+  SKS_TRY(validate_build("sks_sketch_build_counted", c, d_seq, n_bytes, seg_off, n_seg, window, mask, policy));
+  if (policy->kind != SKS_FRAC_MOD)
+    return sks::fail(SKS_E_UNSUPPORTED,
+                     "sks_sketch_build_counted: policy kind: FracMinHash only (a bottom-s sketch's windows are "
+                     "pre-filtered by a threshold, so its records do not count every occurrence)");
+
+  DeviceGuard guard(c->device);
+  BuildState S = build_state(c, window, mask, *policy);
+  S.counted = true;
+  S.min_abund = min_abund;
+  S.max_abund = max_abund;
+  sks_timings tm{};
+  c->last_path = SKS_BUILD_PATH_GENERAL;
+  SKS_HIP(hipEventRecord(c->ev_begin, c->stream));
+
+  // always the general pass loop: the fused single-genome path drops the duplicates it meets
+  Passes P;
+  P.windows.assign(n_seg, 0);
+  P.final_size.assign(n_seg, ~0ull);
+  for (uint32_t g = 0; g < n_seg; ++g)
+    P.plan.push_back(sks::plan_segment(false, policy->param, seg_off[g + 1] - seg_off[g]));
   SKS_TRY(run_passes(S, d_seq, seg_off, n_seg, P, tm));
   SetPtr set;
   SKS_TRY(assemble_set(S, n_seg, P, &set));

@@ -26,6 +26,9 @@ struct BuildState {
   sks::BitRuns runs;
   int key_bits;
   BuildKnobs knobs;
+  // sks_sketch_build_counted: the FracMinHash pipeline also counts, and keeps by these limits
+  bool counted = false;
+  uint32_t min_abund = 0, max_abund = 0xffffffffu;
 };
 
 // The build's environment knobs, in one place (build.cpp).  The SKS_NO_* ones
@@ -46,6 +49,7 @@ inline BuildState build_state(sks_ctx* c, int window, const uint64_t mask[2], co
 // The block is only used on the context's stream.
 struct PassOut {
   DevBlock d;                     // elements (elem_words u64 each)
+  DevBlock abund;                 // a counted build: one u32 per element
   std::vector<uint32_t> segs;
   std::vector<uint64_t> off;      // CSR in elements, size segs.size() + 1
 };

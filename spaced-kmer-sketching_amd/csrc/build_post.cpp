@@ -73,14 +73,22 @@ int post_bottom_fused(BuildState& S, PostIn& in, std::vector<uint64_t>& size, De
   return SKS_OK;
 }
 
-// FracMinHash: the records dense, sorted as `sort` says, then the distinct
-// keys of every segment written out (narrow keys packed for the sorts).
-int post_frac(BuildState& S, PostIn& in, FracSort sort, std::vector<uint64_t>& size, DevBlock& out) {
+// The sorted records of a FracMinHash pass: K the column the runs are found in
+// (128-bit: the high words, K2 the low, else K2 null), `keep` the key bits below
+// a segment tag.
+struct FracSorted {
+  const uint64_t* K = nullptr;
+  const uint64_t* K2 = nullptr;
+  uint64_t keep = ~0ull;
+};
+
+// The first half of the FracMinHash pipelines: the records dense (narrow keys
+// packed for the sorts) and sorted as `sort` says.  The arena is uploaded already.
+int frac_compact_sort(BuildState& S, PostIn& in, FracSort sort, FracSorted* sorted) {
   sks_ctx* c = S.c;
   hipStream_t st = c->stream;
   const uint32_t k = in.k;
   const uint64_t T = in.T, max_len = in.max_len;
-  SKS_TRY(in.arena.upload());
   uint64_t* d_csr = in.d_csr();
   const int mask_lo_bits = end_bit_of(S.mask_lo), mask_hi_bits = end_bit_of(S.mask_hi);
   // tagged: the segment index above the key (128-bit: above the high word)
@@ -97,8 +105,9 @@ int post_frac(BuildState& S, PostIn& in, FracSort sort, std::vector<uint64_t>& s
   if (S.wide)
     SKS_HIP(sks::compact_regions(rec(c, 1), hi, in.d_src(), d_csr, k, max_len, st, nullptr,
                                  tagged ? mask_hi_bits : -1));
-  const uint64_t* K;  // the sorted column the runs are found in (128-bit: the high words, K2 the low)
-  const uint64_t* K2 = nullptr;
+  const uint64_t*& K = sorted->K;
+  const uint64_t*& K2 = sorted->K2;
+  sorted->keep = keep;
   if (S.wide) {
     // (lo, hi) -> sort by lo, then stable by hi  => ascending 128-bit order
     SKS_HIP(sks::seg_sort_pairs(key, col(c, 3), hi, col(c, 4), T, sort_off, d_sort_off, mask_lo_bits, c->tmp, st));
@@ -120,19 +129,128 @@ int post_frac(BuildState& S, PostIn& in, FracSort sort, std::vector<uint64_t>& s
                                st));
     K = col(c, 3);
   }
-  SKS_HIP(sks::seg_unique_scan(K, K2, T, max_len, d_csr, k, flags(c), positions(c), in.d_uniq(), c->tmp, st));
+  return SKS_OK;
+}
+
+// The distinct keys of every sorted segment at their rank among all distinct
+// keys (dense CSR): narrow ones expanded into `out`, wide ones split into
+// columns 7 and 8 and the first `n` interleaved into `out`.
+int frac_scatter_distinct(BuildState& S, PostIn& in, const FracSorted& so, uint64_t n, uint64_t* out) {
+  sks_ctx* c = S.c;
+  hipStream_t st = c->stream;
+  if (!S.wide) {
+    SKS_HIP(sks::seg_unique_scatter(so.K, nullptr, in.T, in.max_len, in.d_csr(), in.k, flags(c), positions(c), nullptr,
+                                    nullptr, out, nullptr, st, &S.runs, so.keep));
+  } else {
+    SKS_HIP(sks::seg_unique_scatter(so.K2, so.K, in.T, in.max_len, in.d_csr(), in.k, flags(c), positions(c), nullptr,
+                                    nullptr, col(c, 7), col(c, 8), st, nullptr, ~0ull, so.keep));
+    SKS_HIP(sks::launch_interleave(col(c, 7), col(c, 8), n, out, st));
+  }
+  return SKS_OK;
+}
+
+// FracMinHash: the records dense, sorted as `sort` says, then the distinct
+// keys of every segment written out.
+int post_frac(BuildState& S, PostIn& in, FracSort sort, std::vector<uint64_t>& size, DevBlock& out) {
+  sks_ctx* c = S.c;
+  hipStream_t st = c->stream;
+  const uint32_t k = in.k;
+  SKS_TRY(in.arena.upload());
+  FracSorted so;
+  SKS_TRY(frac_compact_sort(S, in, sort, &so));
+  SKS_HIP(sks::seg_unique_scan(so.K, so.K2, in.T, in.max_len, in.d_csr(), k, flags(c), positions(c), in.d_uniq(),
+                               c->tmp, st));
   SKS_HIP(sks::pinned_d2h(size.data(), in.d_uniq(), k * sizeof(uint64_t), st));
   uint64_t U = 0;
   for (uint64_t v : size) U += v;
   SKS_TRY(alloc_u64(out, U * S.ew, st));
-  if (!S.wide) {
-    SKS_HIP(sks::seg_unique_scatter(K, nullptr, T, max_len, d_csr, k, flags(c), positions(c), nullptr, nullptr,
-                                    out.as<uint64_t>(), nullptr, st, &S.runs, keep));
-  } else {
-    SKS_HIP(sks::seg_unique_scatter(K2, K, T, max_len, d_csr, k, flags(c), positions(c), nullptr, nullptr, col(c, 7),
-                                    col(c, 8), st, nullptr, ~0ull, keep));
-    SKS_HIP(sks::launch_interleave(col(c, 7), col(c, 8), U, out.as<uint64_t>(), st));
+  return frac_scatter_distinct(S, in, so, U, out.as<uint64_t>());
+}
+
+// The counted FracMinHash pipeline (sks_sketch_build_counted): as post_frac, and
+// the length of every run of equal keys becomes the abundance of its element
+// (abund.hip).  Limits that keep everything: the distinct counts are read back
+// and the elements and run lengths go straight into the pass's blocks.  Other
+// limits: the distinct elements and their run lengths are laid out in working
+// columns (column 2 the runs' first indices, 1 the lengths, 7 or 9 the elements,
+// 0 the bitmap), trimmed by the pass sks_sketch_set_abund_trim runs, chunked by
+// the record counts (which bound the distinct counts the device holds), and the
+// trimmed sizes are read back.  Either way one host round trip.
+int post_frac_counted(BuildState& S, PostIn& in, FracSort sort, std::vector<uint64_t>& size, DevBlock& out,
+                      DevBlock& out_abund) {
+  sks_ctx* c = S.c;
+  hipStream_t st = c->stream;
+  const uint32_t k = in.k;
+  const uint64_t T = in.T, max_len = in.max_len;
+  const bool trims = !abund_keeps_all(S.min_abund, S.max_abund);
+  std::vector<uint64_t> chunk_off, dense_off;
+  size_t o_chunk = 0, o_starts = 0, o_sizes = 0, o_nstarts = 0, o_nsizes = 0;
+  uint64_t n_chunks = 0;
+  if (trims) {
+    std::vector<uint32_t> bound(k);
+    for (uint32_t i = 0; i < k; ++i) {
+      if (in.cnt[i] >> 32)
+        return sks::fail(SKS_E_UNSUPPORTED, "sks_sketch_build_counted: >= 2^32 records in a segment");
+      bound[i] = (uint32_t)in.cnt[i];
+    }
+    chunk_prefixes(bound, &chunk_off, &dense_off);
+    n_chunks = chunk_off[k];
+    o_chunk = in.arena.add(chunk_off);
+    o_starts = in.arena.add_zero(k);
+    o_sizes = in.arena.add_zero(k);   // u32 each, in u64 slots
+    o_nstarts = in.arena.add_zero(k);
+    o_nsizes = in.arena.add_zero(k);  // u32 each
+    // the working columns, flags and positions also serve the trim: sized for both before anything is queued
+    SKS_TRY(reserve_cols(c, {0}, std::max<uint64_t>(T + 1, filter_bitmap_words(n_chunks))));
+    if (S.wide) SKS_TRY(reserve_cols(c, {9}, 2 * (T + 1)));
+    SKS_HIP(c->flag.reserve((std::max<uint64_t>(T, n_chunks) + 1) * sizeof(uint32_t)));
+    SKS_HIP(c->pos.reserve((std::max<uint64_t>(T, n_chunks) + 1) * sizeof(uint64_t)));
   }
+  SKS_TRY(in.arena.upload());
+  uint64_t* d_csr = in.d_csr();
+  FracSorted so;
+  SKS_TRY(frac_compact_sort(S, in, sort, &so));
+  SKS_HIP(sks::seg_unique_scan(so.K, so.K2, T, max_len, d_csr, k, flags(c), positions(c), in.d_uniq(), c->tmp, st));
+  uint64_t* run_start = col(c, 2);
+  if (!trims) {
+    SKS_HIP(sks::pinned_d2h(size.data(), in.d_uniq(), k * sizeof(uint64_t), st));
+    uint64_t U = 0;
+    for (uint64_t v : size) U += v;
+    SKS_TRY(alloc_u64(out, U * S.ew, st));
+    SKS_HIP(out_abund.alloc(std::max<uint64_t>(U, 1) * sizeof(uint32_t), st));
+    SKS_TRY(frac_scatter_distinct(S, in, so, U, out.as<uint64_t>()));
+    SKS_HIP(sks::abund_run_lengths(flags(c), positions(c), d_csr, k, max_len, run_start, out_abund.as<uint32_t>(),
+                                   nullptr, nullptr, st));
+    return SKS_OK;
+  }
+  uint32_t* lengths = reinterpret_cast<uint32_t*>(col(c, 1));
+  uint64_t* distinct = S.wide ? col(c, 9) : col(c, 7);
+  uint64_t* d_starts = in.arena.ptr(o_starts);
+  uint32_t* d_sizes = reinterpret_cast<uint32_t*>(in.arena.ptr(o_sizes));
+  uint64_t* d_nstarts = in.arena.ptr(o_nstarts);
+  uint32_t* d_nsizes = reinterpret_cast<uint32_t*>(in.arena.ptr(o_nsizes));
+  SKS_HIP(sks::abund_run_lengths(flags(c), positions(c), d_csr, k, max_len, run_start, lengths, d_starts, d_sizes,
+                                 st));
+  // the distinct count is on the device only: T bounds it (the interleave of a wide pass moves T pairs)
+  SKS_TRY(frac_scatter_distinct(S, in, so, T, distinct));
+  // the flags and positions are spent: the trim's chunk counters take their place
+  AbundTrimArgs a{distinct, lengths, d_starts, d_sizes, in.arena.ptr(o_chunk), k, S.min_abund, S.max_abund};
+  SKS_HIP(sks::abund_trim_mark(a, n_chunks, col(c, 0), chunk_counts(c), st));
+  SKS_HIP(sks::downsample_offsets(chunk_counts(c), n_chunks, chunk_offs(c), a.chunk_off, k, d_nstarts, d_nsizes,
+                                  c->tmp, st));
+  std::vector<uint32_t> kept(k, 0);
+  SKS_HIP(sks::pinned_d2h(kept.data(), d_nsizes, k * sizeof(uint32_t), st));
+  uint64_t U = 0;
+  for (uint32_t i = 0; i < k; ++i) {
+    if (kept[i] > in.cnt[i])
+      return sks::fail(SKS_E_HIP, "sks_sketch_build_counted: a sketch is larger than its records");
+    size[i] = kept[i];
+    U += kept[i];
+  }
+  SKS_TRY(alloc_u64(out, U * S.ew, st));
+  SKS_HIP(out_abund.alloc(std::max<uint64_t>(U, 1) * sizeof(uint32_t), st));
+  SKS_HIP(sks::abund_trim_scatter(a, S.ew, n_chunks, col(c, 0), chunk_offs(c), out.as<uint64_t>(),
+                                  out_abund.as<uint32_t>(), st));
   return SKS_OK;
 }
 
@@ -291,7 +409,10 @@ int sks::post_process(BuildState& S, const std::vector<uint32_t>& seg_ids, const
   int rc = SKS_OK;
   switch (path.pipe) {
     case PostPipe::kBottomFused: rc = post_bottom_fused(S, in, size, po.d); break;
-    case PostPipe::kFrac: rc = post_frac(S, in, path.sort, size, po.d); break;
+    case PostPipe::kFrac:
+      rc = S.counted ? post_frac_counted(S, in, path.sort, size, po.d, po.abund)
+                     : post_frac(S, in, path.sort, size, po.d);
+      break;
     case PostPipe::kBottomSelect: rc = post_bottom_select(S, in, size, po.d); break;
     case PostPipe::kBottomPairs: rc = post_bottom_pairs(S, in, size, po.d); break;
   }

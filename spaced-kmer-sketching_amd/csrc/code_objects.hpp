@@ -7,7 +7,7 @@
 
 namespace sks {
 
-#define SKS_TU_LIST(X) X(ani) X(cluster) X(downsample) X(filter) X(gather) X(ingress) X(intersect) X(join) X(layout) X(merge) X(post) X(scan) X(search) X(tally) X(topk) X(windows)
+#define SKS_TU_LIST(X) X(abund) X(ani) X(cluster) X(downsample) X(filter) X(gather) X(ingress) X(intersect) X(join) X(layout) X(merge) X(post) X(scan) X(search) X(tally) X(topk) X(windows)
 #define SKS_DECLARE_HOOK(tu) hipError_t code_object_hook_##tu(hipStream_t s);
 SKS_TU_LIST(SKS_DECLARE_HOOK)
 #undef SKS_DECLARE_HOOK

@@ -6,10 +6,11 @@
 // configurations, kmer-sketching.cpp:168).
 //
 // File format "SKSKETCH", little-endian, 8-byte aligned sections.
-// Version 1 (one window / mask for the whole file; every C-ABI set):
+// Version 1 (one window / mask for the whole file; every C-ABI set without
+// abundances) and version 3 (the same with an abundance per element; a counted set):
 //   header (96 bytes)
 //     char     magic[8]   = "SKSKETCH"
-//     uint32   version    = 1
+//     uint32   version    = 1, 2 or 3
 //     uint32   elem_words   1 (window <= 32: one u64 per k-mer) or 2 (lo, hi)
 //     int32    window       w of the spaced seed
 //     int32    policy_kind  sks_policy_kind
@@ -26,22 +27,28 @@
 //   uint64 windows[n]         k-mer windows hashed per genome
 //   [version 2 only] group table, `groups` entries of 32 bytes:
 //     uint32 set, int32 window, uint64 mask_lo, uint64 mask_hi, uint64 size
-//   uint64 data[total * elem_words]   each sketch (v1) / group (v2) sorted ascending, unique
+//   uint64 data[total * elem_words]   each sketch (v1, v3) / group (v2) sorted ascending, unique
+//   [version 3 only] uint32 abund[total]   the abundance (>= 1) of every element, in data's order
+//                             (zero-padded to a multiple of 8 bytes)
 //   char   names[names_bytes] n NUL-terminated strings (when names_bytes > 0)
 //   uint64 checksum           FNV-1a 64 of every byte before it
 // Version 2 is what the C++ facade writes for kmer_sets the reference allows but
 // version 1 cannot hold (kmer.hpp:170-178 accepts any mix of masks): a set is a
 // list of (window, mask) groups in set order, sizes[i] = the sum of set i's
 // group sizes, and the header's window / mask are the first group's.  The C ABI
-// reads version 1 only (an sks_sketch_set has one mask).
+// reads versions 1 and 3 (an sks_sketch_set has one mask); a set without
+// abundances is written as version 1, byte for byte as before version 3 existed.
+// The facade reads versions 1 and 2 and rejects 3 (a kmer_set has no counts).
 // A reader rejects a wrong magic / version, inconsistent sizes, a truncated
-// or over-long file, a checksum mismatch and unsorted sketches (SKS_E_IO).
+// or over-long file, a checksum mismatch, unsorted sketches and a zero abundance
+// (SKS_E_IO).
 #include <cerrno>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "abund_plan.hpp"
 #include "sks.h"
 #include "sks_api_internal.hpp"
 
@@ -52,6 +59,7 @@ namespace {
 constexpr char kMagic[8] = {'S', 'K', 'S', 'K', 'E', 'T', 'C', 'H'};
 constexpr uint32_t kVersion = 1;
 constexpr uint32_t kVersionGroups = 2;
+constexpr uint32_t kVersionAbund = 3;
 
 struct Header {
   char magic[8];
@@ -108,13 +116,15 @@ bool less128(const uint64_t* a, const uint64_t* b, int ew) {
 
 int write_impl(const char* path, const SketchFileMeta& meta, const std::vector<uint32_t>& sizes,
                const std::vector<uint64_t>& windows, const std::vector<SketchGroup>* groups,
-               const uint64_t* data, const std::vector<std::string>& names) {
+               const uint64_t* data, const std::vector<std::string>& names,
+               const std::vector<uint32_t>* abund = nullptr) {
   if (!path) return fail(SKS_E_ARG, "sketch file: null path");
   if (windows.size() != sizes.size() || (!names.empty() && names.size() != sizes.size()))
     return fail(SKS_E_ARG, "sketch file: names / windows must match the number of sketches");
+  if (abund && groups) return fail(SKS_E_ARG, "sketch file: a grouped set holds no abundances");
   Header h{};
   std::memcpy(h.magic, kMagic, 8);
-  h.version = groups ? kVersionGroups : kVersion;
+  h.version = groups ? kVersionGroups : (abund ? kVersionAbund : kVersion);
   h.elem_words = (uint32_t)meta.elem_words;
   h.window = meta.window;
   h.policy_kind = meta.policy.kind;
@@ -136,6 +146,8 @@ int write_impl(const char* path, const SketchFileMeta& meta, const std::vector<u
     if (gtotal != h.total) return fail(SKS_E_ARG, "sketch file: group sizes do not add up");
     h.groups = recs.size();
   }
+  if (abund && abund->size() != h.total)
+    return fail(SKS_E_ARG, "sketch file: one abundance per element is needed");
   std::string table;
   for (const std::string& s : names) {
     if (s.find('\0') != std::string::npos) return fail(SKS_E_ARG, "sketch file: name contains NUL");
@@ -153,6 +165,10 @@ int write_impl(const char* path, const SketchFileMeta& meta, const std::vector<u
   w.put(windows.data(), windows.size() * 8);
   w.put(recs.data(), recs.size() * sizeof(GroupRec));
   w.put(data, h.total * h.elem_words * 8);
+  if (abund) {
+    w.put(abund->data(), h.total * 4);
+    w.put(&zero, abund_section_bytes(h.total) - h.total * 4);
+  }
   w.put(table.data(), table.size());
   const uint64_t sum = w.fnv.h;
   if (w.ok) w.ok = fwrite(&sum, 1, 8, f) == 8;
@@ -164,7 +180,7 @@ int write_impl(const char* path, const SketchFileMeta& meta, const std::vector<u
 int read_impl(const char* path, SketchFileMeta& meta, std::vector<uint32_t>& sizes,
               std::vector<uint64_t>& windows, std::vector<uint64_t>& data,
               std::vector<std::string>& names, std::vector<SketchGroup>* groups,
-              bool* grouped_out = nullptr) {
+              bool* grouped_out = nullptr, std::vector<uint32_t>* abund = nullptr, bool* counted_out = nullptr) {
   if (!path) return fail(SKS_E_ARG, "sketch file: null path");
   FILE* f = fopen(path, "rb");
   if (!f) return fail(SKS_E_IO, std::string("sketch file: cannot open ") + path);
@@ -182,7 +198,8 @@ int read_impl(const char* path, SketchFileMeta& meta, std::vector<uint32_t>& siz
   if (std::memcmp(h.magic, kMagic, 8) != 0) return fail(SKS_E_IO, where + "not a sketch file");
   if (h.version == kVersionGroups && !groups)
     return fail(SKS_E_IO, where + "version 2 (kmer_sets with several masks): load it with sks::load_kmer_sets");
-  if (h.version != kVersion && h.version != kVersionGroups)
+  const bool counted = h.version == kVersionAbund && abund;  // only for a reader that takes abundances
+  if (h.version != kVersion && h.version != kVersionGroups && !counted)
     return fail(SKS_E_IO, where + "unsupported version " + std::to_string(h.version));
   const bool grouped = h.version == kVersionGroups;
   if (h.window < 1 || h.window > 64 || h.elem_words < 1 || h.elem_words > 2 ||
@@ -197,7 +214,8 @@ int read_impl(const char* path, SketchFileMeta& meta, std::vector<uint32_t>& siz
   const size_t o_win = o_sizes + pad8(h.n * 4);
   const size_t o_groups = o_win + h.n * 8;
   const size_t o_data = o_groups + h.groups * sizeof(GroupRec);
-  const size_t o_names = o_data + h.total * h.elem_words * 8;
+  const size_t o_abund = o_data + h.total * h.elem_words * 8;
+  const size_t o_names = o_abund + (counted ? abund_section_bytes(h.total) : 0);
   const size_t body = buf.size() - 8;  // bytes before the checksum
   if (o_names > body || h.names_bytes > body - o_names)
     return fail(SKS_E_IO, where + "length does not match the header");
@@ -217,6 +235,13 @@ int read_impl(const char* path, SketchFileMeta& meta, std::vector<uint32_t>& siz
   uint64_t total = 0;
   for (uint32_t v : sizes) total += v;
   if (total != h.total) return fail(SKS_E_IO, where + "sizes do not add up");
+  if (counted) {
+    abund->resize(h.total);
+    if (h.total) std::memcpy(abund->data(), buf.data() + o_abund, h.total * 4);
+    for (uint32_t a : *abund)
+      if (a == 0) return fail(SKS_E_IO, where + "an abundance is zero");
+  }
+  if (counted_out) *counted_out = counted;
   const int ew = (int)h.elem_words;
   // runs that must each be sorted and unique: the sketches (v1) or the groups (v2)
   std::vector<uint64_t> runs;
@@ -271,8 +296,8 @@ int read_impl(const char* path, SketchFileMeta& meta, std::vector<uint32_t>& siz
 
 int write_sketch_file(const char* path, const SketchFileMeta& meta, const std::vector<uint32_t>& sizes,
                       const std::vector<uint64_t>& windows, const uint64_t* data,
-                      const std::vector<std::string>& names) {
-  return write_impl(path, meta, sizes, windows, nullptr, data, names);
+                      const std::vector<std::string>& names, const std::vector<uint32_t>* abund) {
+  return write_impl(path, meta, sizes, windows, nullptr, data, names, abund);
 }
 
 int write_sketch_file_groups(const char* path, const SketchFileMeta& meta,
@@ -284,8 +309,9 @@ int write_sketch_file_groups(const char* path, const SketchFileMeta& meta,
 
 int read_sketch_file(const char* path, SketchFileMeta& meta, std::vector<uint32_t>& sizes,
                      std::vector<uint64_t>& windows, std::vector<uint64_t>& data,
-                     std::vector<std::string>& names) {
-  return read_impl(path, meta, sizes, windows, data, names, nullptr);
+                     std::vector<std::string>& names, std::vector<uint32_t>* abund, bool* counted) {
+  if (counted) *counted = false;
+  return read_impl(path, meta, sizes, windows, data, names, nullptr, nullptr, abund, counted);
 }
 
 int read_sketch_file_any(const char* path, SketchFileMeta& meta, std::vector<uint32_t>& sizes,

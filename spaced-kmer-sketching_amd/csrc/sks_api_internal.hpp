@@ -31,12 +31,15 @@ struct SketchFileMeta {
 };
 // Writes / reads the format documented in persist.cpp.  `data` holds the
 // sketches back to back (sizes[i] * elem_words words each); names may be empty.
+// With `abund` (one per element) the writer writes version 3, else version 1;
+// a reader given `abund` also takes version 3 and says in *counted which it read.
 int write_sketch_file(const char* path, const SketchFileMeta& meta, const std::vector<uint32_t>& sizes,
                       const std::vector<uint64_t>& windows, const uint64_t* data,
-                      const std::vector<std::string>& names);
+                      const std::vector<std::string>& names, const std::vector<uint32_t>* abund = nullptr);
 int read_sketch_file(const char* path, SketchFileMeta& meta, std::vector<uint32_t>& sizes,
                      std::vector<uint64_t>& windows, std::vector<uint64_t>& data,
-                     std::vector<std::string>& names);
+                     std::vector<std::string>& names, std::vector<uint32_t>* abund = nullptr,
+                     bool* counted = nullptr);
 // Version 2: sets made of (window, mask) groups (the facade's mixed-mask
 // kmer_sets).  `data` holds the groups back to back, in set order.
 struct SketchGroup {

@@ -1,7 +1,8 @@
 // What the C-ABI translation units that run on a device share (ctx.cpp,
 // host_mem.cpp, sketch_set.cpp, kmer_list.cpp, build.cpp, build_post.cpp,
 // pairs.cpp, search_api.cpp, topk_api.cpp, cluster_api.cpp, gather_api.cpp,
-// downsample_api.cpp, merge_rounds.cpp, merge_api.cpp, tally_api.cpp, filter_api.cpp): the
+// downsample_api.cpp, merge_rounds.cpp, merge_api.cpp, tally_api.cpp, filter_api.cpp,
+// abund_api.cpp): the
 // context, the sketch set and k-mer
 // list with the device blocks they own, the error macros, the metadata arena,
 // SketchSpan and the group bounds of the set-level calls (their device-free
@@ -16,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "abund.hpp"
 #include "ani.hpp"
 #include "cluster.hpp"
 #include "code_objects.hpp"
@@ -108,6 +110,9 @@ struct sks_sketch_set {
   sks::DevBlock data;     // elements (elem_words u64 each)
   sks::DevBlock dstarts;  // [n] u64 element index of each sketch
   sks::DevBlock dsizes;   // [n] u32
+  sks::DevBlock abund;    // optional: [total] u32, the abundance of every element (a counted set)
+  uint32_t* d_abund() const { return abund.as<uint32_t>(); }
+  bool has_abund() const { return static_cast<bool>(abund); }
   uint64_t* d_data() const { return data.as<uint64_t>(); }
   uint64_t* d_starts() const { return dstarts.as<uint64_t>(); }
   uint32_t* d_sizes() const { return dsizes.as<uint32_t>(); }
@@ -198,10 +203,12 @@ using SetPtr = std::unique_ptr<sks_sketch_set>;
 enum class MetaUpload { kNone, kStream, kBlocking };
 // The one place that makes a set: fills the host fields (starts from sizes),
 // allocates d_starts and d_sizes and, with `data_words`, d_data of that many
-// words, every block bound to `st`; uploads the metadata as `up` says.
+// words, every block bound to `st`; uploads the metadata as `up` says.  With
+// `abund` the set takes that block (one u32 per element) as its abundances.
 int make_sketch_set(int device, int elem_words, int window, const uint64_t mask[2], const sks_policy& policy,
                     std::vector<uint32_t> sizes, std::vector<uint64_t> windows, std::vector<std::string> names,
-                    const uint64_t* data_words, hipStream_t st, MetaUpload up, SetPtr* out);
+                    const uint64_t* data_words, hipStream_t st, MetaUpload up, SetPtr* out,
+                    DevBlock* abund = nullptr);
 
 inline sks_sketch_info info_of(const sks_sketch_set& s) {
   return {s.window, s.elem_words, {s.mask[0], s.mask[1]}, s.policy, s.n, s.names.empty() ? 0 : 1};

@@ -18,6 +18,7 @@ SKS_FRAC_MOD = 0
 SKS_BOTTOM_S = 1
 SKS_FILTER_SUBTRACT, SKS_FILTER_INTERSECT = 0, 1  # sks_filter_kind
 FILTER_NONE = 0xFFFFFFFF  # a filter_of entry: the sketch is copied unchanged
+ABUND_NO_LIMIT = 0xFFFFFFFF  # max_abund of sks_sketch_build_counted / sks_sketch_set_abund_trim: no upper limit
 TALLY_NO_LIMIT = 0xFFFFFFFF  # a max_count entry of Context.tally: no upper limit
 INTERSECT_AUTO, INTERSECT_MERGE, INTERSECT_JOIN, INTERSECT_GLOBAL = 0, 1, 2, 3
 FRAC_POST_AUTO, FRAC_POST_GENERAL, FRAC_POST_FUSED = 0, 1, 2
@@ -83,6 +84,8 @@ EXPORTED = [
     "sks_gather", "sks_gather_sets", "sks_ctx_set_gather_rounds",
     "sks_search_topk", "sks_search_topk_sets", "sks_sketch_set_filter", "sks_sketch_set_tally",
     "sks_join_layout_region_log", "sks_join_launch_plan",
+    "sks_sketch_build_counted", "sks_sketch_set_has_abund", "sks_sketch_set_device_abund",
+    "sks_sketch_set_abund_copy", "sks_sketch_set_abund_totals", "sks_sketch_set_abund_trim", "sks_abund_pairs",
 ]
 
 # sks_hit (include/sks.h): one record of Context.search's result
@@ -217,6 +220,15 @@ def lib():
     L.sks_sketch_set_filter.argtypes = [vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
     L.sks_sketch_set_tally.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.POINTER(vp), vp,
                                        C.c_uint64]
+    L.sks_sketch_build_counted.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, u64p, C.POINTER(Policy),
+                                           C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.sks_sketch_set_has_abund.argtypes = [vp]
+    L.sks_sketch_set_device_abund.argtypes = [vp]
+    L.sks_sketch_set_device_abund.restype = vp
+    L.sks_sketch_set_abund_copy.argtypes = [vp, C.c_uint32, vp]
+    L.sks_sketch_set_abund_totals.argtypes = [vp, vp]
+    L.sks_sketch_set_abund_trim.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.sks_abund_pairs.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, vp]
     L.sks_kmer_list_build.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, u64p,
                                       C.POINTER(Policy), C.POINTER(vp)]
     L.sks_windows_dense.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, u64p, vp, vp]
@@ -651,6 +663,52 @@ class Context:
                                      C.byref(h)))
         return SketchSet(h)
 
+    def sketch_build_counted(self, d_seq_ptr, n_bytes, seg_off, window, mask, kind=SKS_FRAC_MOD,
+                             param=200, nonce=1, flavour=0, min_abund=1, max_abund=None):
+        """sks_sketch_build_counted: sketch_build that also counts how often every
+        kept k-mer was selected, keeping those with max(min_abund, 1) <= count <=
+        max_abund (None: no limit).  The SketchSet has abundances (SketchSet.abund)."""
+        seg = np.ascontiguousarray(seg_off, dtype=np.uint64)
+        pol = Policy(kind, flavour, param, nonce)
+        h = C.c_void_p()
+        check(lib().sks_sketch_build_counted(self.h, C.c_void_p(d_seq_ptr), n_bytes, seg.ctypes.data,
+                                             len(seg) - 1, window, _mask_arr(mask), C.byref(pol),
+                                             int(min_abund), ABUND_NO_LIMIT if max_abund is None else int(max_abund),
+                                             C.byref(h)))
+        return SketchSet(h)
+
+    def abund_trim(self, sketch_set, min_abund=1, max_abund=None):
+        """sks_sketch_set_abund_trim: the elements of a counted SketchSet with
+        max(min_abund, 1) <= abundance <= max_abund (None: no limit), as a counted set."""
+        h = C.c_void_p()
+        check(lib().sks_sketch_set_abund_trim(self.h, sketch_set.h, int(min_abund),
+                                              ABUND_NO_LIMIT if max_abund is None else int(max_abund), C.byref(h)))
+        return SketchSet(h)
+
+    def abund_pairs(self, samples, refs, a, b):
+        """sks_abund_pairs: for every pair (a[p], b[p]) of a counted sample sketch and
+        a reference sketch, (shared, weight) = (|A n B|, the sum of A's abundances
+        over A n B) as int32 and uint64 numpy arrays; an index outside its set
+        gives shared -1."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        b = np.ascontiguousarray(b, dtype=np.int32)
+        if len(a) != len(b):
+            raise ValueError(f"{len(a)} sample indices for {len(b)} reference indices")
+        n = len(a)
+        d_a = torch.from_numpy(a).to(dev)
+        d_b = torch.from_numpy(b).to(dev)
+        shared = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        weight = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        check(lib().sks_abund_pairs(self.h, samples.h, refs.h, C.c_void_p(d_a.data_ptr()) if n else None,
+                                    C.c_void_p(d_b.data_ptr()) if n else None, n,
+                                    C.c_void_p(shared.data_ptr()) if n else None,
+                                    C.c_void_p(weight.data_ptr()) if n else None))
+        self.synchronize()
+        return shared.cpu().numpy()[:n].copy(), weight.cpu().numpy()[:n].view(np.uint64).copy()
+
     def kmer_list(self, d_seq_ptr, n_bytes, seg_off, window, mask, c=200, nonce=1, flavour=0):
         """nucleotide_string_list_to_kmers on the device: returns (positions,
         bits[n, 4] = kmer_bits lo, hi, masked lo, hi, counts per segment)."""
@@ -1083,6 +1141,23 @@ class SketchSet:
         if self.elem_words == 1:
             return np.stack([buf, np.zeros_like(buf)], axis=1)
         return buf.reshape(-1, 2)
+
+    def has_abund(self):
+        """Whether the set carries an abundance per element (a counted set)."""
+        return int(lib().sks_sketch_set_has_abund(self.h))
+
+    def abund(self, i):
+        """The abundances of sketch i's elements, a uint32 array in the elements' order."""
+        n = int(self.sizes()[i])
+        buf = np.zeros(max(n, 1), dtype=np.uint32)
+        check(lib().sks_sketch_set_abund_copy(self.h, i, buf.ctypes.data))
+        return buf[:n]
+
+    def abund_totals(self):
+        """The sum of every sketch's abundances, a uint64 array of n entries."""
+        out = np.zeros(max(self.n, 1), dtype=np.uint64)
+        check(lib().sks_sketch_set_abund_totals(self.h, out.ctypes.data))
+        return out[:self.n]
 
     def copy_into(self, i, host_ptr):
         """Sketch i (size * elem_words u64) into caller memory (e.g. pinned); returns size."""
